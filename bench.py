@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — BASELINE.json headline metric: GCXS(CSR) x dense SpMM on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak] [--full] [--dump-outputs DIR]
     python bench.py --workload spgemm [--gpus N] [--steps K] [--warmup W]      BASELINE configs[4] (bench_spgemm.py), same schema
 
 Workload (BASELINE.json configs[1]): A = CSR 10^6 x 10^4 at 1 % (exactly 10^8 stored elements, uniform, sorted column
@@ -9,9 +9,16 @@ indices, int32 indices, explicit compressed_axes=(0,)), B = dense 10^4 x 128 fp3
 Inputs are generated on the device (synthetic) and are resident in HBM before the timed region.  One "step" = one
 product through the product API (`sparse_amd.matmul`, the reference's NaN pass of `matmul` INCLUDED).  The product path
 caches a K-tiled block stream of A on the array at its first product (inspector/executor: C ABI `spamd_spmm_tiled*`,
-csrc/spmm_tiled.hip); `value` is the steady state of repeated products with the same A, and the same line carries what
-a FIRST product costs (`config.first_call_ms` = inspector + executor with a warm allocator, `first_call_cold_ms` = the
-same in a fresh process, `rowgroup_ms` = the general cache-less kernel).  `--no-tiled` benches the row-group kernel only.
+csrc/spmm_tiled.hip); `value` is the steady state of repeated products with the same A.  With `--full` the same line
+carries what a FIRST product costs (`config.first_call_ms` = inspector + executor with a warm allocator,
+`first_call_cold_ms` = the same in a fresh process, `rowgroup_ms` = the general cache-less kernel).  `--no-tiled` benches
+the row-group kernel only.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` = wall time of the K timed steps / K, `config`); every other measurement is
+behind `--full`.  `--dump-outputs DIR` writes, after the timed steps, what the last timed step returned (C = A @ B, see
+`dump_outputs`) as DIR/<name>.npy; the inputs are generated from fixed seeds, so two runs with the same arguments (and
+two builds of the project) can be compared output for output.
 
 N > 1: `python bench.py --gpus N` re-launches itself under `python -m torch.distributed.run` (one rank per GPU, RCCL);
 launched by torch.distributed.run directly it reads RANK / LOCAL_RANK / WORLD_SIZE.  Two modes:
@@ -20,9 +27,9 @@ launched by torch.distributed.run directly it reads RANK / LOCAL_RANK / WORLD_SI
                               exchange step); C stays row-sharded.  value = total flops / max-over-ranks time.
   --scaling weak              every rank owns its own 10^6-row block of an (N*10^6) x 10^4 matrix; same exchange.
 
-The JSON line also carries `roofline` (HBM-bound: algorithmic bytes of one launch / the kernel's average duration,
-measured with HIP events around K back-to-back launches of the executor on the launch stream; `traffic` is read from the
-committed rocprofv3 PMC pass and labelled with its source), on rank 0 at N=1 `cpu_baseline` (the oracle's single-thread
+With `--full` the JSON line also carries `roofline` (HBM-bound: algorithmic bytes of one launch / the kernel's average
+duration, measured with HIP events around K back-to-back launches of the executor on the launch stream; `traffic` is read
+from the committed rocprofv3 PMC pass and labelled with its source), on rank 0 at N=1 `cpu_baseline` (the oracle's single-thread
 C restatement of the reference loop, rebuilt with -march=native on this box, plus SciPy's csr @ dense as an independent
 cross-check) and `paths`: the other rows of SURVEY.md section 8 at BASELINE.json's sizes (bench_paths.py).
 """
@@ -130,6 +137,36 @@ def dev_time(fn, reps):
     e1.record()
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) / reps
+
+
+DUMP_SAMPLE_BYTES = 40 << 20    # whole rows of C, sampled
+DUMP_SUMS_MAX = 1 << 21         # float64 sums: 16 MB
+
+
+def dump_outputs(path, c, rank, world):
+    """Write what the last timed step returned, C (this rank's row block), as float32 / float64 .npy files under `path`,
+    at most 64 MB in all ranks together:
+      c_rows_sample      whole rows of C (float32) at a fixed, seeded sample of row numbers (<= 40 MB)
+      c_sample_rows      those row numbers (float64)
+      c_row_sums         the float64 sum of every row of C - of every run of ceil(rows / 2^21) consecutive rows beyond 2^21 rows
+      c_col_sums         the float64 sum of every column of C
+    With more than one rank every name carries `_rank<r>`."""
+    os.makedirs(path, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    c = torch.as_tensor(c)
+    rows, cols = int(c.shape[0]), int(c.shape[1])
+    take = min(rows, max(1, DUMP_SAMPLE_BYTES // world // (cols * 4 + 8)))    # a float32 row and its float64 number
+    pick = np.sort(np.random.default_rng(20240501 + rank).choice(rows, take, replace=False)) if rows else np.zeros(0, np.int64)
+    sample = c[torch.from_numpy(pick).to(c.device)].float()
+    sums = c.sum(1, dtype=torch.float64)
+    cap = max(1, DUMP_SUMS_MAX // world)
+    if rows > cap:
+        grp = -(-rows // cap)
+        sums = torch.nn.functional.pad(sums, (0, -(-rows // grp) * grp - rows)).view(-1, grp).sum(1)
+    out = {"c_rows_sample": sample.cpu().numpy(), "c_sample_rows": pick.astype(np.float64),
+           "c_row_sums": sums.cpu().numpy(), "c_col_sums": c.sum(0, dtype=torch.float64).cpu().numpy()}
+    for name, arr in out.items():
+        np.save(os.path.join(path, f"{name}{sfx}.npy"), arr)
 
 
 def cpu_baseline(data, idx, ptr, b, M, N, gpu_out):
@@ -298,8 +335,12 @@ def main():
     ap.add_argument("--n", type=int, default=128)
     ap.add_argument("--density", type=float, default=0.01)
     ap.add_argument("--idx", choices=["int32", "int64"], default="int32")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-paths", action="store_true", help="skip the other section-8 rows (`paths`)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: first-product costs, the default-settings loop, the "
+                         "executor alone (roofline), the scaling proxy, cpu_baseline and the other section-8 rows (`paths`)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one returned as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-paths", action="store_true", help="with --full: skip the other section-8 rows (`paths`)")
     ap.add_argument("--no-nan-check", action="store_true", help="switch matmul's NaN pass off in the timed region")
     ap.add_argument("--exact", action="store_true", help="bit-exact mul+add instead of FMA")
     ap.add_argument("--no-tiled", action="store_true", help="row-group kernel only (no cached block stream)")
@@ -319,6 +360,8 @@ def main():
     if args.workload == "spgemm":
         import bench_spgemm
 
+        if args.dump_outputs:
+            raise SystemExit("bench.py --dump-outputs: the spmm workload only")
         if "--steps" not in sys.argv:
             args.steps = 3          # a step is ~90 ms of products at N = 1
         if "--warmup" not in sys.argv:
@@ -382,7 +425,7 @@ def main():
             return _dist.sharded_spmm(a, b_shard, K, memo=memo, prefetch=b_shard if prefetch else None)
         return sparse_amd.matmul(a, b_full)
 
-    # ---- what a FIRST product with this A costs (rank-local; all of it outside the timed region) -----------------------
+    # ---- what a FIRST product with this A costs (--full; rank-local; all of it outside the timed region) ----------------
     rowgroup_ms = first_call_cold_ms = first_call_ms = inspector_ms = None
     tiled = False
     if _dot._tiled_eligible(a.data, b_full, (Mloc, N), K):
@@ -394,13 +437,15 @@ def main():
             _dot.drop_derived(a)               # forget the cached block stream: inspector + executor, as at a first product
             return _dot._gcxs_times_dense(a, b_full, (Mloc, N))
 
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        first_product()
-        torch.cuda.synchronize()
-        first_call_cold_ms = (time.perf_counter() - t0) * 1e3   # fresh process: includes ~1 GB of first-time allocations
-        first_call_ms = dev_time(first_product, 3)             # warm allocator (a program that has multiplied before)
-        inspector_ms = dev_time(lambda: _kernels.csr_tiled_layout(data, idx, ptr, Mloc, K), 3)
+        if args.full:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            first_product()
+            torch.cuda.synchronize()
+            first_call_cold_ms = (time.perf_counter() - t0) * 1e3   # fresh process: includes ~1 GB of first-time allocations
+            first_call_ms = dev_time(first_product, 3)             # warm allocator (a program that has multiplied before)
+            inspector_ms = dev_time(lambda: _kernels.csr_tiled_layout(data, idx, ptr, Mloc, K), 3)
+        # the block stream every step reads, cached on `a` here as the first product would (the first product's own path)
         tiled = _dot.prepare_spmm(a)
 
     # the value is a STEADY-STATE rate: the first ~30 products after the set-up above (host-timed first products, the
@@ -437,9 +482,13 @@ def main():
         nnz_ranks = [nnz]
     wall = float(tmax.item())
     ms_per_step = wall / args.steps * 1e3
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, world)
+
+    # ---- everything below the headline: --full only --------------------------------------------------------------------
     ms_static_b = ms_prefetch = None
     secondary_error = None
-    if sharded_b:
+    if sharded_b and args.full:
         def timed_loop(**kw):
             step(**kw)
             torch.cuda.synchronize()
@@ -471,7 +520,7 @@ def main():
     # verdict before it returns, as the reference's `matmul` has its warning raised inside the call) - printed beside the
     # headline, which runs with the verdicts deferred to `flush_warnings()` (round-5 verdict, item 9)
     ms_default = None
-    if world == 1:
+    if world == 1 and args.full:
         _settings.NAN_WARNING = "sync"
         for _ in range(3):
             step()
@@ -484,29 +533,31 @@ def main():
         _settings.NAN_WARNING = "deferred"
 
     # ---- the dominant kernel alone: K back-to-back launches of the executor between two HIP events --------------------
-    if tiled:
-        layout = a._tiled_layouts[torch.float32]
-        kern = lambda: _kernels.dot_csr_ndarray_tiled(layout, (Mloc, N), K, b_full, out=out, exact=bool(args.exact))
-    else:
-        kern = lambda: _kernels.dot_csr_ndarray((Mloc, N), data, idx, ptr, b_full, exact=bool(args.exact), out=out)
-    kern()
-    kernel_ms = dev_time(kern, args.steps)
-    if tiled:
-        for _ in range(3):
-            rowgroup()
-        rowgroup_ms = dev_time(rowgroup, 5)   # the general cache-less kernel (every dtype / shape the executor does not take)
+    kernel_ms = None
+    if args.full:
+        if tiled:
+            layout = a._tiled_layouts[torch.float32]
+            kern = lambda: _kernels.dot_csr_ndarray_tiled(layout, (Mloc, N), K, b_full, out=out, exact=bool(args.exact))
+        else:
+            kern = lambda: _kernels.dot_csr_ndarray((Mloc, N), data, idx, ptr, b_full, exact=bool(args.exact), out=out)
+        kern()
+        kernel_ms = dev_time(kern, args.steps)
+        if tiled:
+            for _ in range(3):
+                rowgroup()
+            rowgroup_ms = dev_time(rowgroup, 5)   # the general cache-less kernel (every dtype / shape the executor does not take)
     # ---- what one GPU can say about scaling (no 8-GPU node is available to this run): for world sizes 2, 4, 8
     # EVERY block of the nnz-balanced partition of THIS matrix is timed alone (B resident, through `matmul`): the step time
     # of the sharded product is the MAX over the blocks + the exchange; its fixed part (an RCCL all-gather of B launched at
     # world size 1) is measured in a child process
     proxy = None
-    if world == 1 and tiled and not args.no_paths:   # (not in the profiled headline run: its kernel average must be the headline's alone)
+    if args.full and world == 1 and tiled and not args.no_paths:   # (not in the profiled headline run: its kernel average must be the headline's alone)
         try:
             proxy = scaling_proxy(sparse_amd, _dist, data, idx, ptr, b_full, K, ms_per_step, args.steps)
         except Exception as e:   # noqa: BLE001 - the headline line must still be printed
             proxy = {"error": repr(e)}
     nan_check_ms = None
-    if _settings.NAN_CHECK:
+    if args.full and _settings.NAN_CHECK:
         # what `matmul` adds to a product: the scans of both operands (A's verdict is memoised per buffer version, so in the
         # steady state this is the scan of B and the bookkeeping), HIP events around the scans alone
         def scans():
@@ -521,11 +572,6 @@ def main():
         total_nnz = sum(nnz_ranks)
         flops_total = 2.0 * total_nnz * N
         flops_local = 2.0 * nnz * N
-        ib = 4 if idt == torch.int32 else 8
-        rd, wr = algorithmic_bytes(Mloc, K, N, nnz, 4, ib)
-        ach = (rd + wr) / (kernel_ms * 1e-3) / 1e9
-        traffic, traffic_src = load_traffic("spmm_tiled" if tiled else "spmm_csr")
-        lds_floor = nnz * N * 4 / LDS_READ_PEAK_BPS * 1e3
         r4 = lambda x: None if x is None else round(x, 4)
         line = {
             "metric": "GCXS x dense SpMM throughput (GFLOP/s)",
@@ -554,7 +600,14 @@ def main():
                 "first_call_ms": r4(first_call_ms), "first_call_cold_ms": r4(first_call_cold_ms),
                 "inspector_ms": r4(inspector_ms), "rowgroup_ms": r4(rowgroup_ms),
             },
-            "roofline": {
+        }
+        if args.full:
+            ib = 4 if idt == torch.int32 else 8
+            rd, wr = algorithmic_bytes(Mloc, K, N, nnz, 4, ib)
+            ach = (rd + wr) / (kernel_ms * 1e-3) / 1e9
+            traffic, traffic_src = load_traffic("spmm_tiled" if tiled else "spmm_csr")
+            lds_floor = nnz * N * 4 / LDS_READ_PEAK_BPS * 1e3
+            line["roofline"] = {
                 "bound": "hbm", "achieved": round(ach, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "frac": round(ach / HBM_PEAK_GBS, 5), "frac_of_measured_copy_rate": round(ach / HBM_MEASURED_GBS, 5),
                 "traffic": traffic, "traffic_source": traffic_src,
@@ -567,14 +620,13 @@ def main():
                 "scaling_proxy": proxy,
                 "ablation": TILED_ABLATION_FILE if tiled else None,
                 "what": "rank 0: algorithmic bytes of its row block / mean of `steps` back-to-back executor launches (HIP events)",
-            },
-        }
-        if world == 1 and not args.no_cpu:
+            }
+        if args.full and world == 1 and not args.no_cpu:
             try:
                 line["cpu_baseline"] = cpu_baseline(data, idx, ptr, b_full, Mloc, N, out)
             except Exception as e:  # the bench line must still be printed
                 line["cpu_baseline"] = {"error": repr(e)}
-        if world == 1 and not args.no_paths:
+        if args.full and world == 1 and not args.no_paths:
             del out
             # the other section-8 rows: the FULL dict goes to an earlier stdout line and to gpurun_out/paths.json; the LAST
             # line (the one the driver parses; round 4's 23 KB line did not parse) carries compact maps only

@@ -122,7 +122,7 @@ def _run_bench_under_launcher(extra):
 
 
 def test_bench_runs_under_the_distributed_launcher():
-    line = _run_bench_under_launcher(["--steps", "2", "--warmup", "1", "--no-cpu", "--no-paths"])
+    line = _run_bench_under_launcher(["--full", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-paths"])
     assert line["n_gpus"] == 1 and line["steps"] == 2 and line["unit"] == "GFLOP/s" and line["value"] > 0
     assert line["config"]["world_size"] == 1 and "roofline" in line and 0 < line["roofline"]["frac"] < 1
 

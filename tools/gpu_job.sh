@@ -5,7 +5,7 @@
 # jobs (several may be chained with `--`; every job's output also lands under gpurun_out/<tag>/, tag = $GPU_JOB_TAG or "job"):
 #     tests [pytest args]         python -m pytest <args or `tests`> -x -q -m gpu
 #     rows <A1,A9,...>            bench_paths.py --rows <list>, one compact line per row (tools/r05/show_rows.py)
-#     bench [bench.py args]       bench.py (default --steps 20 --warmup 5): the last (driver-parsed) line and its size
+#     bench [bench.py args]       bench.py (default --full --steps 20 --warmup 5): the last line and its size
 #     small [args]                bench_small.py (the reference's own benchmark sizes)
 #     py <script> [args]          any script of tools/ (timing sweeps, probes)
 #     variants <script> <v...>    the script once per library variant (sparse_amd/_lib/variants/libsparse_amd_<v>.so; "" = the default)
@@ -22,7 +22,7 @@ run_job() {
     rows)
       timeout 900 python bench_paths.py --rows "$1" > gpurun_out/$tag/rows.txt 2>&1; python tools/r05/show_rows.py gpurun_out/$tag/rows.txt; grep -i "error\|Traceback" -A3 gpurun_out/$tag/rows.txt | head -12 ;;
     bench)
-      args=("$@"); [ ${#args[@]} -eq 0 ] && args=(--steps 20 --warmup 5)
+      args=("$@"); [ ${#args[@]} -eq 0 ] && args=(--full --steps 20 --warmup 5)
       timeout 900 python bench.py "${args[@]}" > gpurun_out/$tag/bench_stdout.txt 2> gpurun_out/$tag/bench_stderr.txt
       tail -1 gpurun_out/$tag/bench_stdout.txt > gpurun_out/$tag/bench_line.json; wc -c gpurun_out/$tag/bench_line.json
       python -c "import json,sys; d=json.load(open('gpurun_out/$tag/bench_line.json')); print({k: d[k] for k in ('value','ms_per_step')}, {k: d['roofline'].get(k) for k in ('frac','kernel_ms','scaling_proxy')}, d.get('cpu_baseline', {}).get('value'))" ;;

@@ -1,9 +1,9 @@
-"""python tools/publish_profiles.py <rNN>: copy the outputs of tools/run_profiles.sh <rNN> (gpurun_out/<rNN>) into profiles/ and
+"""python tools/publish_profiles.py <rNN>: copy the outputs of tools/run_profiles.sh <rNN> (bench_out/<rNN>) into profiles/ and
 refresh profiles/traffic.json."""
 import csv, json, os, shutil, sys
 RND = sys.argv[1] if len(sys.argv) > 1 else 'r05'
 NUM = int(RND.lstrip('r'))
-src = f'gpurun_out/{RND}'
+src = f'bench_out/{RND}'
 shutil.copy(f'{src}/bench_line.json', f'profiles/{RND}_bench_line.json')
 shutil.copy(f'{src}/stats/b_kernel_stats.csv', f'profiles/{RND}_bench_kernel_stats.csv')
 shutil.copy(f'{src}/stats_headline/b_kernel_stats.csv', f'profiles/{RND}_headline_kernel_stats.csv')
@@ -28,7 +28,7 @@ k['round'] = NUM
 k.update({'FETCH_SIZE_KB_per_launch': flat['FETCH_SIZE'], 'WRITE_SIZE_KB_per_launch': flat['WRITE_SIZE'], 'traffic_bytes_per_launch': rd + wr,
           'TCC_HIT_sum': flat['TCC_HIT_sum'], 'TCC_MISS_sum': flat['TCC_MISS_sum'], 'TCC_REQ_sum': flat['TCC_REQ_sum'],
           'SQ_WAVE_CYCLES': wc, 'SQ_WAIT_ANY': flat['SQ_WAIT_ANY'], 'SQ_WAIT_INST_ANY': flat['SQ_WAIT_INST_ANY'], 'SQ_ACTIVE_INST_ANY': flat['SQ_ACTIVE_INST_ANY']})
-k['rocprof_source'] = (f"profiles/{RND}_headline_kernel_stats.csv (rocprofv3 --kernel-trace --stats -- python bench.py --steps 20 --warmup 5 --no-cpu "
+k['rocprof_source'] = (f"profiles/{RND}_headline_kernel_stats.csv (rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 20 --warmup 5 --no-cpu "
                        f"--no-paths; the same run reports kernel_ms by HIP events in profiles/{RND}_headline_profiled_line.json)")
 k['note'] = (f"round {NUM}: counters re-collected on this round's library (the fp32 executor's phase code is unchanged since late round 2; "
              "round 5 made its group index 32-bit and added the optional row map of balanced layouts)")

@@ -1,4 +1,4 @@
-"""Summarise an evidence run (tools/run_profiles.sh <rNN> -> gpurun_out/<rNN>): per kernel (name prefix) the rocprofv3 average duration and, from the PMC passes over
+"""Summarise an evidence run (tools/run_profiles.sh <rNN> -> bench_out/<rNN>): per kernel (name prefix) the rocprofv3 average duration and, from the PMC passes over
 bench_paths.py, the fabric-side bytes per launch (reads = 2 * FETCH_SIZE * 1024 on gfx950, writes = WRITE_SIZE * 1024:
 MI355X_MICROARCH.md, HBM section), the L2 hit rate and the LDS / wave-cycle counters.  -> JSON on stdout."""
 import csv, glob, json, os, re, sys
