@@ -227,7 +227,9 @@ def reduce_impl(x, method, axis=(0,), keepdims=False, _no_merge=False, **kwargs)
     plan = _SCALAR_PLANS.get(plan_key) if plan_key is not None else None
     if plan is None:
         zero_reduce_result = method.reduce([fv, fv], **kwargs)
-        dense_result = not equivalent(zero_reduce_result, fv) and super_ufunc is None
+        # (any / all of a non-zero fill: logical_or(3, 3) is True, the same truth value - the fill becomes bool(fill))
+        fv_as = np.bool_(fv) if name in ("logical_or", "logical_and") else fv
+        dense_result = not equivalent(zero_reduce_result, fv_as) and super_ufunc is None
         if plan_key is not None:
             plan = {"dense": dense_result}
             if len(_SCALAR_PLANS) > 512:
@@ -344,7 +346,8 @@ def reduce_impl(x, method, axis=(0,), keepdims=False, _no_merge=False, **kwargs)
                                          res_np_dtype != np.dtype(bool) else vals[:0].view(torch.bool), (),
                                          np.asarray(value).astype(res_np_dtype)[()], torch.int64)
         if n_eq:    # results equal to the fill value are not stored (rare: a sum that cancels exactly, a max of zeros)
-            flags = K.flag_ne_bits(vals, final_fill if vals.dtype != torch.uint8 else np.uint8(bool(final_fill)))
+            # (uint8 words hold bools AND uint8 values: a uint8 max of 1 is not a fill of 3)
+            flags = K.flag_ne_bits(vals, np.uint8(bool(final_fill)) if res_np_dtype == np.dtype(bool) else final_fill)
             offs = K.exclusive_scan(flags)
             gids, vals = K.compact(gids, flags, offs, count - n_eq), K.compact(vals, flags, offs, count - n_eq)
     else:

@@ -28,7 +28,7 @@ _TO_BOOL = {"greater", "greater_equal", "less", "less_equal", "equal", "not_equa
 _BITWISE = {"bitwise_and", "bitwise_or", "bitwise_xor", "left_shift", "right_shift"}
 _UNARY = {"negative": "negative", "absolute": "absolute", "fabs": "absolute", "positive": "positive",
           "logical_not": "logical_not", "square": None}
-_DTYPES = {np.dtype("float32"), np.dtype("float64"), np.dtype("int32"), np.dtype("int64"), np.dtype("bool")}
+_DTYPES = {np.dtype("float32"), np.dtype("float64"), np.dtype("int32"), np.dtype("int64"), np.dtype("uint8"), np.dtype("bool")}
 
 
 class Untraceable(Exception):
@@ -155,7 +155,7 @@ def _as(t, np_dtype):
 def run(root, arrays, n, devi):
     """Replay the graph: `arrays[i]` = device tensor (n elements) of positional argument i (only array arguments are
     looked up).  Returns the device tensor of the root (n elements, root dtype)."""
-    from ._umath import _BIN, _UN, binary_arrays, unary_array
+    from ._umath import _BIN, _COMP_TYPES, _UN, binary_arrays, unary_array
 
     memo = {}
 
@@ -216,8 +216,8 @@ def run(root, arrays, n, devi):
                     name = "logical_and"
                 elif comp == np.dtype(bool) and op in ("subtract", "divide"):
                     raise Untraceable("boolean subtract / divide")
-                if name not in _BIN:
-                    raise Untraceable(f"no device kernel for {name}")
+                if name not in _BIN or (comp not in _COMP_TYPES.get(_BIN[name], (comp,)) and comp != np.dtype(bool)):
+                    raise Untraceable(f"no device kernel for {name} in {comp}")
                 r = binary_arrays(name, ta, tb, a_scalar=sa, b_scalar=sb)
                 if r.dtype == torch.uint8 and out_dt == np.dtype(bool):
                     r = r.view(torch.bool)

@@ -38,6 +38,7 @@ _UN = {"negative": 0, "absolute": 1, "abs": 1, "fabs": 1, "sqrt": 2, "exp": 3, "
        "log10": 24, "exp2": 25, "arcsinh": 26, "arctanh": 27, "cbrt": 28, "deg2rad": 29, "radians": 29,
        "rad2deg": 30, "degrees": 30, "isnan": 64, "isinf": 65, "isfinite": 66, "logical_not": 67, "signbit": 68,
        "conjugate": 22, "conj": 22, "real": 22}
+_UN_INT = {0, 1, 15, 16, 17, 18, 19, 20, 22}       # unary ops `un_tt` evaluates on integer (and bool) values
 _TO_BOOL_BIN = set(range(32, 41))
 _BOOL_ARITH = {"add": "logical_or", "maximum": "logical_or", "fmax": "logical_or",
                "multiply": "logical_and", "minimum": "logical_and", "fmin": "logical_and"}
@@ -56,24 +57,33 @@ def binary_arrays(name, a, b, a_scalar=False, b_scalar=False, out_bool_as=torch.
     else:
         code = _BIN[name]
     devi = require_hip(a, b)
+    was_bool = a.dtype == torch.bool and b.dtype == torch.bool
     a, b = _as_u8(a.contiguous()), _as_u8(b.contiguous())
     if a.dtype != b.dtype:
         raise TypeError(f"binary_arrays needs one compute dtype, got {a.dtype} and {b.dtype}")
     n = int(b.numel() if a_scalar else a.numel())
+    if code == 6 and not b.dtype.is_floating_point and b.dtype != torch.uint8 and b.numel():
+        # NumPy's integer power refuses negative exponents; the kernel's squaring loop would return 1 for them
+        neg = binary_arrays("less", b, torch.zeros(1, dtype=b.dtype, device=devi), b_scalar=True, out_bool_as=torch.uint8)
+        if K.count_eq_bits(neg, 0) != neg.numel():
+            raise ValueError("Integers to negative integer powers are not allowed.")
     out_dtype = torch.uint8 if code in _TO_BOOL_BIN else a.dtype
     out = torch.empty(n, dtype=out_dtype, device=devi)
     _ffi.call("spamd_ewise_binary", code, _CODE[a.dtype], n, ptr(a), int(a_scalar), ptr(b), int(b_scalar), ptr(out),
               stream_ptr(devi))
-    return out.view(torch.bool) if (code in _TO_BOOL_BIN and out_bool_as == torch.bool) else out
+    if code in _TO_BOOL_BIN:
+        return out.view(torch.bool) if out_bool_as == torch.bool else out
+    return out.view(torch.bool) if was_bool else out      # (bool & bool, bool | bool, ...: bool)
 
 
 def unary_array(name, a):
     code = _UN[name]
     devi = require_hip(a)
+    was_bool = a.dtype == torch.bool
     a = _as_u8(a.contiguous())
     out = torch.empty(a.numel(), dtype=torch.uint8 if code >= 64 else a.dtype, device=devi)
     _ffi.call("spamd_ewise_unary", code, _CODE[a.dtype], a.numel(), ptr(a), ptr(out), stream_ptr(devi))
-    return out.view(torch.bool) if code >= 64 else out
+    return out.view(torch.bool) if code >= 64 or was_bool else out   # (bool in, bool out: |x|, floor(x), ... of 0 / 1 bytes)
 
 
 def select(mask, a, b):
@@ -215,6 +225,7 @@ def merge_union(name, ka, va, kb, vb, fill_a, fill_b, fill_out):
     `va`/`vb` share the compute dtype; `fill_out` is a NumPy scalar of the output dtype."""
     code = _BIN[name]
     devi = require_hip(ka, kb, va, vb)
+    bool_out = code in _TO_BOOL_BIN or (va.dtype == torch.bool and vb.dtype == torch.bool)
     va, vb = _as_u8(va.contiguous()), _as_u8(vb.contiguous())
     comp_np = dev.np_dtype(va.dtype) if va.dtype != torch.uint8 else np.dtype("uint8")
     na, nb = int(ka.numel()), int(kb.numel())
@@ -222,7 +233,7 @@ def merge_union(name, ka, va, kb, vb, fill_a, fill_b, fill_out):
     nblocks = int(_ffi.lib().spamd_merge_num_blocks(na, nb))
     if nblocks == 0:
         e = torch.empty(0, dtype=out_t, device=devi)
-        return torch.empty(0, dtype=torch.int64, device=devi), (e.view(torch.bool) if code in _TO_BOOL_BIN else e)
+        return torch.empty(0, dtype=torch.int64, device=devi), (e.view(torch.bool) if bool_out else e)
     s = stream_ptr(devi)
     fa, fb = _bits(fill_a, comp_np), _bits(fill_b, comp_np)
     fo = _bits(fill_out, np.dtype("uint8") if code in _TO_BOOL_BIN else comp_np)
@@ -243,7 +254,7 @@ def merge_union(name, ka, va, kb, vb, fill_a, fill_b, fill_out):
             keys, vals = keys[:total].clone(), vals[:total].clone()
         else:
             keys, vals = keys[:total], vals[:total]
-        return keys, (vals.view(torch.bool) if code in _TO_BOOL_BIN else vals)
+        return keys, (vals.view(torch.bool) if bool_out else vals)
     part = torch.empty(nblocks + 1, dtype=torch.int64, device=devi)
     _ffi.call("spamd_merge_partition", na, ptr(ka), nb, ptr(kb), ptr(part), s)
     counts = torch.empty(nblocks + 2, dtype=torch.int64, device=devi)
@@ -258,14 +269,14 @@ def merge_union(name, ka, va, kb, vb, fill_a, fill_b, fill_out):
             keys, vals = keys[:total].clone(), vals[:total].clone()
         else:
             keys, vals = keys[:total], vals[:total]
-        return keys, (vals.view(torch.bool) if code in _TO_BOOL_BIN else vals)
+        return keys, (vals.view(torch.bool) if bool_out else vals)
     _ffi.call("spamd_merge_union", 0, *args, ptr(counts), 0, 0, 0, s)
     offs = K.exclusive_scan(counts[:nblocks + 1])   # n counts + one ignored slot (the last slot is single-pass only)
     total = int(offs[-1])
     keys = torch.empty(total, dtype=torch.int64, device=devi)
     vals = torch.empty(total, dtype=out_t, device=devi)
     _ffi.call("spamd_merge_union", 1, *args, 0, ptr(offs), ptr(keys), ptr(vals), s)
-    return keys, (vals.view(torch.bool) if code in _TO_BOOL_BIN else vals)
+    return keys, (vals.view(torch.bool) if bool_out else vals)
 
 
 def _where(proc, finish):
@@ -785,10 +796,18 @@ def elemwise(func, *args, **kwargs):
         if name not in _UN or kwargs or x.data.dtype not in _CODE:   # (complex / narrow value types: host-evaluated func)
             return _elemwise_general(func, proc, kwargs, dtype_kw, finish)
         fill = _np_result(func, np.asarray(x.fill_value))[()]
-        data = x.data
-        if data.dtype in (torch.int32, torch.int64, torch.bool) and fill.dtype.kind == "f":
-            data = K.convert(data, torch_dtype(fill.dtype))
-        res = unary_array(name, data)
+        code, in_np = _UN[name], np.dtype(x.dtype)
+        if code >= 64:
+            comp_np = in_np                 # predicates: evaluated on the stored type, bytes out
+        elif fill.dtype in _F:
+            comp_np = fill.dtype            # integer / bool data converted to NumPy's float result first
+        elif fill.dtype == in_np and code in _UN_INT:
+            comp_np = in_np
+        else:
+            # NumPy's result type is one the kernel does not compute (float16 from uint8 / bool, int8 from bool
+            # square / reciprocal), or `un_tt` has no integer form of the op (integer reciprocal: 1.0 / x cast back)
+            return _elemwise_general(func, proc, kwargs, dtype_kw, finish)
+        res = unary_array(name, K.convert(x.data, torch_dtype(comp_np)))
         if dtype_kw is not None:
             res, fill = K.convert(res, torch_dtype(dtype_kw)), fill.astype(dtype_kw)
         return finish(x.linear_loc(), res, shape, np.asarray(fill)[()], devi)

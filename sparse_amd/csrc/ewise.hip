@@ -262,9 +262,9 @@ __device__ __forceinline__ T un_tt(int op, T x) {
       case U_ABS: return fabs(x);
       case U_SQRT: return sqrt(x);
       case U_EXP: return exp(x);
-      case U_EXPM1: return expm1(x);
+      case U_EXPM1: return x == T(0) ? x : expm1(x);   // (the device library returns +0 for -0: C99 keeps the sign)
       case U_LOG: return log(x);
-      case U_LOG1P: return log1p(x);
+      case U_LOG1P: return x == T(0) ? x : log1p(x);
       case U_LOG2: return log2(x);
       case U_LOG10: return log10(x);
       case U_EXP2: return exp2(x);
@@ -287,8 +287,10 @@ __device__ __forceinline__ T un_tt(int op, T x) {
       case U_SQUARE: return x * x;
       case U_RECIP: return T(1) / x;
       case U_POS: return x;
-      case U_DEG2RAD: return x * T(0.017453292519943295);
-      case U_RAD2DEG: return x * T(57.29577951308232);
+      // NumPy's constants are NPY_PI / 180 and 180 / NPY_PI divided in T: for float32 the second one is 1 ulp below
+      // float(180 / pi)
+      case U_DEG2RAD: return x * (T(3.141592653589793238462643383279502884) / T(180));
+      case U_RAD2DEG: return x * (T(180) / T(3.141592653589793238462643383279502884));
     }
   } else {
     switch (op) {
