@@ -81,7 +81,7 @@ int spamd_spmm_csr(int val_dtype, int idx_dtype, int64_t M, int64_t K, int64_t N
 
 /* The same product with B RESIDENT IN LDS, for a short contracted axis (`_dot_csr_ndarray` / `_dot_coo_ndarray` as
  * tensordot uses them, `_common.py:720-755, 979-1014`; BASELINE config 3: K = 512): a 256-byte column panel of B —
- * (K + 1) * 256 bytes <= 144 KB, i.e. K <= 575 — is copied into LDS once per workgroup, 16 lanes own a row of A and read a
+ * (K + 1) * 256 bytes <= 160 KB, i.e. K <= 639 — is copied into LDS once per workgroup, 16 lanes own a row of A and read a
  * row of B per stored element from LDS instead of through the vector-memory path.  Sums run in storage order per output
  * element (bit-identical to spamd_spmm_csr's row-group kernel in both arithmetic modes; SPAMD_EXACT_MULADD as there).
  * spamd_spmm_csr itself takes this path when `spamd_spmm_csr_ldsb_fits` says 1, M >= 8192 and N * itemsize >= 128, unless
@@ -108,9 +108,13 @@ int spamd_spmm_csr_ldsb(int val_dtype, int idx_dtype, int64_t M, int64_t K, int6
  * chunk of columns (<= 4, 8-byte values: 3) whose K x w values fit the LDS; 0 = not this kernel - and spamd_spmm_csr_stream
  * runs them, one launch per chunk (b and out may be strided: ldb, ldo).  A pass costs A's stream whatever its width, so
  * spamd_spmm_csr takes up to 3 passes for 5 <= N <= SPAMD_STREAM_MULTI_MAX_N, up to 2 for N <= 4 columns of 8-byte values
- * and 1 for N <= 4 columns of 4-byte values, under the conditions above. */
+ * and 1 for N <= 4 columns of 4-byte values, under the conditions above.
+ * `spamd_spmm_csr_stream_passes`: that whole rule - the passes spamd_spmm_csr takes with these `flags`, 0 = another kernel
+ * (host arithmetic only; a_data / a_indices are only tested for alignment). */
 #define SPAMD_STREAM_MULTI_MAX_N 12
 int spamd_spmm_csr_stream_fits(int val_dtype, int64_t M, int64_t K, int64_t N, const void* a_data, const void* a_indices);
+int spamd_spmm_csr_stream_passes(int val_dtype, int64_t M, int64_t K, int64_t N, const void* a_data, const void* a_indices,
+                                 unsigned flags);
 int spamd_spmm_csr_stream(int val_dtype, int idx_dtype, int64_t M, int64_t K, int64_t N,
                           const void* a_data, const void* a_indices, const void* a_indptr,
                           const void* b, int64_t ldb, void* out, int64_t ldo,

@@ -8,6 +8,7 @@ torch tensors already on the device (zero-copy, result stays on the device).
 """
 import builtins
 import warnings
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -479,24 +480,14 @@ def _return_kind(return_type):
     raise TypeError(f"unsupported return_type {return_type!r}")
 
 
-def _tiled_dtype(data, bt):
-    """value type of the tiled kernel for this product (the reference's result dtype rule `_dot_dtype`,
-    _common.py:635-636, restricted to what the kernel covers): float32 x float32, or float64 with float32/64."""
-    if data.dtype == torch.float32 and bt.dtype == torch.float32:
-        return torch.float32
-    if {data.dtype, bt.dtype} <= {torch.float32, torch.float64}:
-        return torch.float64
-    if data.dtype == torch.int32 and bt.dtype == torch.int32:
-        return torch.int32      # (round 4: exact wrap-around products, the executor's int32 variant)
-    return None
-
-
 LDSB_MAX_K = 639      # (K + 1) rows of 256 bytes within the 160 KB of LDS: `spamd_spmm_csr_ldsb_fits` (575 / 144 KB until late round 4)
 
 
-def _tiled_eligible(data, bt, out_shape, Kd):
-    """The inspector/executor kernel covers float32 and float64 products whose B is (padded to) whole 128- / 64-column
-    panels; from N = 5 (float32: 8 until late round 4) on the padded product beats the row-group kernel (round 3, config-2 operand:
+def _executor_dtype(M, Kd, N, nnz, vdtype, bdtype, tiled_spmm):
+    """Value type of the inspector/executor kernel for an (M x Kd, nnz stored elements) @ (Kd x N) product, None when it does
+    not take it.  The value type is the reference's result dtype rule (`_dot_dtype`, _common.py:635-636) restricted to what the
+    kernel covers: float32 x float32, float64 with float32/64, int32 x int32 (round 4: exact wrap-around products), with B
+    (padded to) whole 128- / 64-column panels; from N = 5 (float32: 8 until late round 4) on the padded product beats the row-group kernel (round 3, config-2 operand:
     fp32 N = 8 / 16 / 32: 0.80 vs 1.14 / 1.17 / 1.18 ms, fp64 N = 5 / 8 / 16: 1.02 vs 1.17 / 1.33 / 1.32 ms;
     `NARROW=1 tools/rowgroup_shapes.py`; late round 4, tools/r04/narrow_n.py: fp32 N = 5 / 6 / 7 0.84 / 0.77 / 0.83 vs 0.86 /
     1.08 / 0.83 ms - odd widths paid a slice of the padded result; with the single-column store of the straddling lane
@@ -504,20 +495,35 @@ def _tiled_eligible(data, bt, out_shape, Kd):
     measured on MI355X (tools/tiled_crossover.py, tools/r04/m_crossover.py): enough rows for the width (`_tiled_min_rows`)
     and enough stored elements per 32 x 128 cells for the width (`_tiled_min_density`: 5-12).  The inspector costs about one row-group product, so
     a single product breaks even and every further one is 2-3x faster."""
-    M, N = out_shape
-    if _settings.TILED_SPMM == "never" or bt.dim() != 2:
-        return False
-    dt = _tiled_dtype(data, bt)
-    if dt is None or N < 5:   # narrower results: the row-vector kernel
-        return False
-    if (Kd + 512) * N * bt.element_size() >= (1 << 32):   # the executor walks B with 32-bit byte offsets (buffer-form tile DMA)
-        return False
-    if Kd <= LDSB_MAX_K and N * bt.element_size() >= 128:
+    if tiled_spmm == "never" or N < 5:   # narrower results: the row-vector kernel
+        return None
+    if vdtype == torch.float32 and bdtype == torch.float32:
+        dt = torch.float32
+    elif {vdtype, bdtype} <= {torch.float32, torch.float64}:
+        dt = torch.float64
+    elif vdtype == torch.int32 and bdtype == torch.int32:
+        dt = torch.int32
+    else:
+        return None
+    b_item = bdtype.itemsize
+    if (Kd + 512) * N * b_item >= (1 << 32):   # the executor walks B with 32-bit byte offsets (buffer-form tile DMA)
+        return None
+    if Kd <= LDSB_MAX_K and N * b_item >= 128:
         # a short contracted axis: `spamd_spmm_csr` keeps a column panel of B in LDS by itself (spmm_ldsb.hip) - as fast as
         # the executor on these shapes (config 3: 0.13-0.15 ms against 0.143 ms) without an inspector or a second copy of A
-        return False
-    per_list = int(data.numel()) * 4096 / max(M * Kd, 1)
-    return M >= _tiled_min_rows(N * dt.itemsize) and per_list >= _tiled_min_density(N * dt.itemsize, Kd * N * bt.element_size())
+        return None
+    per_list = nnz * 4096 / max(M * Kd, 1)
+    if M >= _tiled_min_rows(N * dt.itemsize) and per_list >= _tiled_min_density(N * dt.itemsize, Kd * N * b_item):
+        return dt
+    return None
+
+
+def _tiled_eligible(data, bt, out_shape, Kd):
+    """Does the inspector/executor kernel take `data`'s matrix @ `bt` (before the stream, COO and hub-row overrides of
+    `_spmm_route`)?  See `_executor_dtype`."""
+    M, N = out_shape
+    return bt.dim() == 2 and _executor_dtype(int(M), int(Kd), int(N), int(data.numel()), data.dtype, bt.dtype,
+                                             _settings.TILED_SPMM) is not None
 
 
 def _tiled_min_density(row_bytes, b_bytes):
@@ -637,10 +643,10 @@ def prepare_operand(a, b_like):
         if isinstance(v, _Verdict):
             _PENDING_PREP.append(v)     # read (and memoised on `a`) by the next `matmul` through `_drain_prepared`
     if isinstance(a, GCXS) or getattr(a, "_tiled_layouts", None):
-        data = a.data if _csc_without_twin(a) else _csr_triplet(a)[0]
-        out_shape = (int(a.shape[0]), int(b_like.shape[1]))
-        if _tiled_eligible(data, b_like, out_shape, int(a.shape[1])):
-            prepare_spmm(a, _tiled_dtype(data, b_like))
+        # (the route as far as it is known without device work: a hub split is taken into account once it has been found)
+        r = _route_of(a, b_like, (int(a.shape[0]), int(b_like.shape[1])), None if _csc_without_twin(a) else _csr_triplet(a))
+        if r.dt is not None and not r.takes_hub(a.__dict__.get("_hot_split")):
+            prepare_spmm(a, r.dt)
 
 
 _PENDING_PREP = []   # NaN scans started by `prepare_operand`, not read yet
@@ -780,7 +786,7 @@ def _hot_row_split(a, data, indices, indptr):
     res = None
     M = int(indptr.numel()) - 1
     nnz = int(data.numel())
-    if nnz >= HOT_ROW_MIN_NNZ and M >= 1 and not a.__dict__.get("_no_hot_split") and indptr.dtype in (torch.int32, torch.int64):
+    if M >= 1 and not a.__dict__.get("_no_hot_split") and indptr.dtype in (torch.int32, torch.int64):
         lens = binary_arrays("subtract", indptr[1:].clone(), indptr[:-1].contiguous())     # (the clone: an aligned start)
         longest = int(reduce_all(lens, "maximum")[1])
         if longest >= HOT_ROW_MIN:
@@ -841,47 +847,87 @@ def _hot_product(split, bt, out_shape):
     return out
 
 
-def _gcxs_times_dense(a, bt, out_shape):
-    """GCXS or canonical 2-D COO times dense."""
-    from ._coo import COO
+class _Route(NamedTuple):
+    """How one `sparse @ dense` product runs (`_spmm_route`)."""
+    kind: str                 # "tiled_csc": the executor from a block stream of a csc operand's own arrays (no CSR twin);
+                              # "tiled": the executor from a block stream of the CSR arrays; "stream": `passes` passes of the
+                              # stream kernel; "spmm_csr": the kernel `spamd_spmm_csr` picks (ldsb, row-vector, row-group)
+    dt: torch.dtype = None    # the executor's value type
+    passes: int = 0
+    hub_from: int = None      # not None: the hub-row split runs instead when the operand has one (`_hot_row_split`) whose
+                              # longest row holds at least this many elements
+    count: bool = False       # a COO operand's eligible product: counted in `_spmm_uses`
+    plan: bool = False        # register a `_SpmmPlan` for the operand's later products
 
-    _validate_derived(a)
-    Kd = int(a.shape[1])
-    direct = _csc_without_twin(a)     # (eligibility needs the values' count and type only: no CSR twin for the executor's sake)
-    data = a.data if direct else None
-    if direct and not (_tiled_eligible(data, bt, out_shape, Kd) and
-                       (a.nnz >= CSC_INSPECT_MIN_NNZ or (getattr(a, "_tiled_layouts", None) or {}).get(_tiled_dtype(data, bt)))):
-        direct = False
-    if not direct:
-        data, indices, indptr = _csr_triplet(a)
-        if HOT_ROW_SPLIT and not _settings.EXACT_MULADD and int(out_shape[1]) > 0 and \
-                K.torch_dtype(K.dot_dtype(data.dtype, bt.dtype)) in _HOT_COMBINE_TYPES:
-            split = _hot_row_split(a, data, indices, indptr)
-            if split is not None and (split[5] >= HOT_ROW_MIN_STREAM or not (
-                    int(out_shape[1]) <= K.STREAM_MULTI_MAX_N and K.stream_passes(
-                        int(out_shape[0]), Kd, int(out_shape[1]), K.torch_dtype(K.dot_dtype(data.dtype, bt.dtype)), data, indices))):
-                return _hot_product(split, bt, out_shape)
-    use_tiled = eligible = _tiled_eligible(data, bt, out_shape, Kd)
-    if use_tiled and not direct and out_shape[1] <= K.STREAM_MULTI_MAX_N and not (
-            _settings.EXACT_MULADD and _tiled_dtype(data, bt).is_floating_point):
+    def takes_hub(self, split):
+        return self.hub_from is not None and split is not None and split[5] >= self.hub_from
+
+
+def _spmm_route(M, Kd, N, nnz, vdtype, bdtype, form, cached, coo_uses, data_ptr, idx_ptr, tiled_spmm, exact, hot_split):
+    """The one choice of kernel for an (M x Kd, nnz stored elements, values `vdtype`) @ (Kd x N, `bdtype`) product.  Pure
+    (plain values in, a `_Route` out; the stream rule is asked of the library's host code): the caller builds the CSR twin,
+    runs the hub-row probe, counts a COO's products and builds block streams.
+      form: "csr" (CSR arrays at data_ptr / idx_ptr), "csc" (a csc operand without its CSR twin; the twin, should the route
+        need it, is built in fresh aligned buffers) or "coo" (a canonical 2-D COO, CSR arrays at data_ptr / idx_ptr);
+      cached: value types of the operand's block streams; coo_uses: a COO's eligible products so far;
+      tiled_spmm / exact / hot_split: `_settings.TILED_SPMM`, `_settings.EXACT_MULADD`, `HOT_ROW_SPLIT`."""
+    dt = _executor_dtype(M, Kd, N, nnz, vdtype, bdtype, tiled_spmm)
+    if form == "csc" and dt is not None and (nnz >= CSC_INSPECT_MIN_NNZ or dt in cached):
+        # (eligibility needs the values' count and type only: no CSR twin for the executor's sake)
+        return _Route("tiled_csc", dt)
+    dtr = K.torch_dtype(K.dot_dtype(vdtype, bdtype))
+    passes = 0
+    if dtr in _HOT_COMBINE_TYPES:
+        passes = K.stream_passes(M, Kd, N, dtr, data_ptr, idx_ptr, _ffi.EXACT_MULADD if exact else 0)
+    hub_from = None
+    if hot_split and not exact and N > 0 and dtr in _HOT_COMBINE_TYPES and nnz >= HOT_ROW_MIN_NNZ:
+        hub_from = HOT_ROW_MIN_STREAM if passes else 0
+    if passes:
         # a result of 5-12 columns from CSR arrays that are there anyway: two or three passes of the stream kernel over A
         # (0.36-0.53 ms at config 2's matrix) instead of the executor's padded 128-column panel (0.77 ms) - and no inspector
-        dt = _tiled_dtype(data, bt)
-        if K.stream_passes(int(out_shape[0]), Kd, int(out_shape[1]), dt, data, indices):
-            use_tiled = eligible = False
-    if use_tiled and isinstance(a, COO) and not getattr(a, "_tiled_layouts", None):
-        # COO operands of `tensordot` are usually temporaries (an N-D array reshaped to 2-D): for small ones the inspector
-        # only pays when the array is multiplied again (config 3, 1.3 x 10^6 elements: 0.33 ms with a fresh layout per call
-        # against 0.14), so such a COO gets its block stream at its SECOND eligible product.  From COO_TILED_FIRST_NNZ stored
-        # elements on the first product already takes it: the fixed part of a fresh layout (allocations, three launches,
-        # the verdict read-back: ~0.15 ms) is then below what the executor saves over the cache-less kernel (config 2's
-        # size: inspector 0.57 + executor 0.85 ms against 2.8 ms).
-        a._spmm_uses = getattr(a, "_spmm_uses", 0) + 1
-        use_tiled = a._spmm_uses >= 2 or _coo_first_product_tiled(int(data.numel()), out_shape[1] * _tiled_dtype(data, bt).itemsize)
-    if use_tiled:
+        dt = None
+    # COO operands of `tensordot` are usually temporaries (an N-D array reshaped to 2-D): for small ones the inspector
+    # only pays when the array is multiplied again (config 3, 1.3 x 10^6 elements: 0.33 ms with a fresh layout per call
+    # against 0.14), so such a COO gets its block stream at its SECOND eligible product.  From COO_TILED_FIRST_NNZ stored
+    # elements on the first product already takes it: the fixed part of a fresh layout (allocations, three launches,
+    # the verdict read-back: ~0.15 ms) is then below what the executor saves over the cache-less kernel (config 2's
+    # size: inspector 0.57 + executor 0.85 ms against 2.8 ms).
+    count = dt is not None and form == "coo" and not cached
+    if dt is not None and (not count or coo_uses >= 1 or _coo_first_product_tiled(nnz, N * dt.itemsize)):
         # the inspector costs about one product (1.25 ms at config 2 against 0.85 ms per tiled and 2.8 ms per
         # row-group product), so it runs at the first eligible product and is cached on the array
-        dt = _tiled_dtype(data, bt)
+        return _Route("tiled", dt, hub_from=hub_from, count=count)
+    # (no plan for an eligible COO that waits for its second product: it must keep counting its products)
+    return _Route("stream" if passes else "spmm_csr", passes=passes, hub_from=hub_from, count=count, plan=dt is None)
+
+
+def _route_of(a, b, out_shape, triplet):
+    """`_spmm_route` of `a @ b` from what `a` holds now; `triplet`: its CSR arrays, None for a csc operand without its twin."""
+    from ._coo import COO
+
+    form = "csc" if triplet is None else ("coo" if isinstance(a, COO) else "csr")
+    return _spmm_route(int(out_shape[0]), int(a.shape[1]), int(out_shape[1]), int(a.data.numel()), a.data.dtype, b.dtype, form,
+                       tuple(getattr(a, "_tiled_layouts", None) or ()), getattr(a, "_spmm_uses", 0),
+                       0 if triplet is None else dev.ptr(triplet[0]), 0 if triplet is None else dev.ptr(triplet[1]),
+                       _settings.TILED_SPMM, _settings.EXACT_MULADD, HOT_ROW_SPLIT)
+
+
+def _gcxs_times_dense(a, bt, out_shape):
+    """GCXS or canonical 2-D COO times dense, by the route `_spmm_route` chooses."""
+    _validate_derived(a)
+    Kd = int(a.shape[1])
+    triplet = None if _csc_without_twin(a) else _csr_triplet(a)
+    r = _route_of(a, bt, out_shape, triplet)
+    if r.kind != "tiled_csc":
+        data, indices, indptr = triplet or _csr_triplet(a)
+        if r.hub_from is not None:
+            split = _hot_row_split(a, data, indices, indptr)
+            if r.takes_hub(split):
+                return _hot_product(split, bt, out_shape)
+    if r.count:
+        a._spmm_uses = getattr(a, "_spmm_uses", 0) + 1
+    if r.dt is not None:
+        dt = r.dt
         prepare_spmm(a, dt)
         M, N = out_shape
         panel = 64 if dt == torch.float64 else 128
@@ -896,10 +942,9 @@ def _gcxs_times_dense(a, bt, out_shape):
             return _tiled_product(a, dt, (M, N), Kd, bp)
         return _tiled_product(a, dt, out_shape, Kd, bt)
     res = K.dot_csr_ndarray(out_shape, data, indices, indptr, bt, exact=_settings.EXACT_MULADD)
-    if a.ndim == 2 and not eligible:     # (an eligible COO that waits for its second product must keep counting its products)
+    if r.plan:
         _register_plan(a, bt, out_shape, (data, indices, indptr))
     return res
-
 
 
 def _dot(a, b, return_type=None):

@@ -152,6 +152,7 @@ SIGNATURES = {
     "spamd_transpose_2d": (_int, [_int, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     "spamd_spmm_csr_stream": (_int, [_int, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _u32, _vp]),
     "spamd_spmm_csr_stream_fits": (_int, [_int, _i64, _i64, _i64, _vp, _vp]),
+    "spamd_spmm_csr_stream_passes": (_int, [_int, _i64, _i64, _i64, _vp, _vp, _u32]),
     "spamd_spmm_csr_ldsb_fits": (_int, [_int, _i64, _i64, _i64, _vp, _i64, _vp, _i64]),
 }
 

@@ -685,7 +685,7 @@ static int stream_chunk_width(size_t es, int64_t K) {
 // 0 = the stream form does not take this product; otherwise the number of PASSES over A it takes: ceil(N / chunk width) - 1
 // for results of at most 4 (8-byte values: 3) columns whose B fits the LDS (round 6: a pass costs what A's stream costs
 // whatever its width - 0.16-0.18 ms at config 2's matrix, 0.25 with 8-byte values - so two or three passes beat the padded
-// panel of the tiled executor, 0.77 / 1.0 ms; the caller decides how many passes are worth it: spamd_stream_passes_worth).
+// panel of the tiled executor, 0.77 / 1.0 ms; how many passes are worth it: spamd_spmm_csr_stream_passes).
 extern "C" int spamd_spmm_csr_stream_fits(int val_dtype, int64_t M, int64_t K, int64_t N, const void* a_data,
                                           const void* a_indices) {
   if (M <= 0 || M >= spamd::ST_MAX_ROWS || K <= 0 || N < 1 || N > 64) return 0;

@@ -458,3 +458,163 @@ def test_hub_row_piece_plan():
             assert (np.diff(vfirst) == -(-pieces_per_row // D.HOT_COMBINE_FAN)).all() and vfirst[-1] == len(g1) - 1
     v, f, g = D.hot_piece_plan([0], [4096])
     assert v.tolist() == list(range(0, 4097, 32)) and f.tolist() == [0, 128] and g is None
+
+
+_A, _A2, _MIS = 0x7F0000000000, 0x7F0000100000, 0x7F0000000004      # aligned, aligned, misaligned by 4 bytes
+
+# (id, M, K, N, nnz, value dtype, B dtype, operand form, value types of its cached block streams, a COO's eligible products so
+# far, address of the CSR values, of the column indices, TILED_SPMM, EXACT_MULADD, HOT_ROW_SPLIT, what the hub probe finds
+# (longest row, rows of at least HOT_ROW_MIN elements) or None, route).  The routes were evaluated with the predicates of the
+# commit before `_spmm_route` (its `_tiled_eligible`, `_tiled_dtype`, `_kernels.stream_passes`, `_coo_first_product_tiled` and the
+# branch conditions of its `_gcxs_times_dense` / `dot_csr_ndarray`), on stand-ins for the operands: a case on each side of
+# every threshold, and the shapes where this rule and `spamd_spmm_csr`'s own ldsb rule disagree ("disagree-*": kept as they are).
+_SPMM_ROUTES = [
+    ('float32-N1-K3000', 70000, 3000, 1, 2100000, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('stream', None, 1, False, True)),
+    ('float32-N1-K11000', 70000, 11000, 1, 2100000, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('stream', None, 1, False, True)),
+    ('float32-N4-K3000', 70000, 3000, 4, 2100000, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('stream', None, 1, False, True)),
+    ('float32-N4-K11000', 70000, 11000, 4, 2100000, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('spmm_csr', None, 0, False, True)),
+    ('float32-N5-K3000', 70000, 3000, 5, 2100000, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('stream', None, 2, False, True)),
+    ('float32-N5-K11000', 70000, 11000, 5, 2100000, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('stream', None, 2, False, True)),
+    ('float32-N8-K3000', 70000, 3000, 8, 2100000, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('stream', None, 2, False, True)),
+    ('float32-N8-K11000', 70000, 11000, 8, 2100000, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('stream', None, 3, False, True)),
+    ('float32-N12-K3000', 70000, 3000, 12, 2100000, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('stream', None, 3, False, True)),
+    ('float32-N12-K11000', 70000, 11000, 12, 2100000, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('spmm_csr', None, 0, False, True)),
+    ('float32-N13-K3000', 70000, 3000, 13, 2100000, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('tiled', 'float32', 0, False, False)),
+    ('float32-N13-K11000', 70000, 11000, 13, 2100000, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('spmm_csr', None, 0, False, True)),
+    ('float64-N1-K3000', 70000, 3000, 1, 2100000, 'float64', 'float64', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('stream', None, 1, False, True)),
+    ('float64-N1-K7000', 70000, 7000, 1, 2100000, 'float64', 'float64', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('stream', None, 1, False, True)),
+    ('float64-N1-K11000', 70000, 11000, 1, 2100000, 'float64', 'float64', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('stream', None, 1, False, True)),
+    ('float64-N3-K3000', 70000, 3000, 3, 2100000, 'float64', 'float64', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('stream', None, 1, False, True)),
+    ('float64-N3-K7000', 70000, 7000, 3, 2100000, 'float64', 'float64', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('stream', None, 2, False, True)),
+    ('float64-N3-K11000', 70000, 11000, 3, 2100000, 'float64', 'float64', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('spmm_csr', None, 0, False, True)),
+    ('float64-N4-K3000', 70000, 3000, 4, 2100000, 'float64', 'float64', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('stream', None, 2, False, True)),
+    ('float64-N4-K7000', 70000, 7000, 4, 2100000, 'float64', 'float64', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('stream', None, 2, False, True)),
+    ('float64-N4-K11000', 70000, 11000, 4, 2100000, 'float64', 'float64', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('spmm_csr', None, 0, False, True)),
+    ('float64-N5-K3000', 70000, 3000, 5, 2100000, 'float64', 'float64', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('stream', None, 2, False, True)),
+    ('float64-N5-K7000', 70000, 7000, 5, 2100000, 'float64', 'float64', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('stream', None, 3, False, True)),
+    ('float64-N5-K11000', 70000, 11000, 5, 2100000, 'float64', 'float64', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('spmm_csr', None, 0, False, True)),
+    ('float64-N9-K3000', 70000, 3000, 9, 2100000, 'float64', 'float64', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('stream', None, 3, False, True)),
+    ('float64-N9-K7000', 70000, 7000, 9, 2100000, 'float64', 'float64', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('tiled', 'float64', 0, False, False)),
+    ('float64-N9-K11000', 70000, 11000, 9, 2100000, 'float64', 'float64', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('spmm_csr', None, 0, False, True)),
+    ('float64-N10-K3000', 70000, 3000, 10, 2100000, 'float64', 'float64', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('tiled', 'float64', 0, False, False)),
+    ('float64-N10-K7000', 70000, 7000, 10, 2100000, 'float64', 'float64', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('tiled', 'float64', 0, False, False)),
+    ('float64-N10-K11000', 70000, 11000, 10, 2100000, 'float64', 'float64', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('spmm_csr', None, 0, False, True)),
+    ('float64-N12-K3000', 70000, 3000, 12, 2100000, 'float64', 'float64', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('tiled', 'float64', 0, False, False)),
+    ('float64-N12-K7000', 70000, 7000, 12, 2100000, 'float64', 'float64', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('tiled', 'float64', 0, False, False)),
+    ('float64-N12-K11000', 70000, 11000, 12, 2100000, 'float64', 'float64', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('spmm_csr', None, 0, False, True)),
+    ('float64-N13-K3000', 70000, 3000, 13, 2100000, 'float64', 'float64', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('tiled', 'float64', 0, False, False)),
+    ('float64-N13-K7000', 70000, 7000, 13, 2100000, 'float64', 'float64', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('tiled', 'float64', 0, False, False)),
+    ('float64-N13-K11000', 70000, 11000, 13, 2100000, 'float64', 'float64', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('spmm_csr', None, 0, False, True)),
+    ('int32-N4', 70000, 3000, 4, 2100000, 'int32', 'int32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('stream', None, 1, False, True)),
+    ('int32-N5', 70000, 3000, 5, 2100000, 'int32', 'int32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('stream', None, 2, False, True)),
+    ('int32-N12', 70000, 3000, 12, 2100000, 'int32', 'int32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('stream', None, 3, False, True)),
+    ('int32-N13', 70000, 3000, 13, 2100000, 'int32', 'int32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('tiled', 'int32', 0, False, False)),
+    ('int64-N4', 70000, 3000, 4, 2100000, 'int64', 'int64', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('stream', None, 2, False, True)),
+    ('int64-N5', 70000, 3000, 5, 2100000, 'int64', 'int64', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('stream', None, 2, False, True)),
+    ('int64-N12', 70000, 3000, 12, 2100000, 'int64', 'int64', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('spmm_csr', None, 0, False, True)),
+    ('int64-N13', 70000, 3000, 13, 2100000, 'int64', 'int64', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('spmm_csr', None, 0, False, True)),
+    ('f32xf64-N8', 70000, 3000, 8, 2100000, 'float32', 'float64', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('stream', None, 3, False, True)),
+    ('f64xf32-N8', 70000, 3000, 8, 2100000, 'float64', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('stream', None, 3, False, True)),
+    ('rows32767-N4', 32767, 3000, 4, 983010, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('spmm_csr', None, 0, False, True)),
+    ('rows32767-N8', 32767, 3000, 8, 983010, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('spmm_csr', None, 0, False, True)),
+    ('rows32768-N4', 32768, 3000, 4, 983040, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('stream', None, 1, False, True)),
+    ('rows32768-N8', 32768, 3000, 8, 983040, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('stream', None, 2, False, True)),
+    ('misaligned-data-N8', 70000, 3000, 8, 2100000, 'float32', 'float32', 'csr', (), 0, _MIS, _A2, 'auto', False, True, None, ('tiled', 'float32', 0, False, False)),
+    ('misaligned-idx-N4', 70000, 3000, 4, 2100000, 'float32', 'float32', 'csr', (), 0, _A, _MIS, 'auto', False, True, None, ('spmm_csr', None, 0, False, True)),
+    ('misaligned-idx-f64-N4', 70000, 3000, 4, 2100000, 'float64', 'float64', 'csr', (), 0, _A, _MIS, 'auto', False, True, None, ('spmm_csr', None, 0, False, True)),
+    ('exact-f32-N8', 70000, 3000, 8, 2100000, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', True, True, None, ('tiled', 'float32', 0, False, False)),
+    ('exact-f32-N4', 70000, 3000, 4, 2100000, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', True, True, None, ('spmm_csr', None, 0, False, True)),
+    ('exact-i32-N8', 70000, 3000, 8, 2100000, 'int32', 'int32', 'csr', (), 0, _A, _A2, 'auto', True, True, None, ('stream', None, 2, False, True)),
+    ('exact-f32-N128', 70000, 3000, 128, 2100000, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', True, True, None, ('tiled', 'float32', 0, False, False)),
+    ('never-f32-N128', 70000, 3000, 128, 2100000, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'never', False, True, None, ('spmm_csr', None, 0, False, True)),
+    ('never-f32-N8', 70000, 3000, 8, 2100000, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'never', False, True, None, ('stream', None, 2, False, True)),
+    ('never-csc-N128', 70000, 3000, 128, 2100000, 'float32', 'float32', 'csc', (), 0, _A, _A2, 'never', False, True, None, ('spmm_csr', None, 0, False, True)),
+    ('ldsb-f32-N31-K639', 300000, 639, 31, 608423, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('tiled', 'float32', 0, False, False)),
+    ('ldsb-f32-N31-K640', 300000, 640, 31, 609375, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('tiled', 'float32', 0, False, False)),
+    ('ldsb-f32-N32-K639', 300000, 639, 32, 608423, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('spmm_csr', None, 0, False, True)),
+    ('ldsb-f32-N32-K640', 300000, 640, 32, 609375, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('tiled', 'float32', 0, False, False)),
+    ('minrows-1panel-M45055', 45055, 3000, 128, 329993, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('spmm_csr', None, 0, False, True)),
+    ('minrows-1panel-M45056', 45056, 3000, 128, 330000, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('tiled', 'float32', 0, False, False)),
+    ('minrows-2panels-M20479', 20479, 3000, 256, 149993, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('spmm_csr', None, 0, False, True)),
+    ('minrows-2panels-M20480', 20480, 3000, 256, 150000, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('tiled', 'float32', 0, False, False)),
+    ('minrows-f64-1panel-M45056', 45056, 3000, 64, 330000, 'float64', 'float64', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('tiled', 'float64', 0, False, False)),
+    ('density-1panel-9-', 100000, 3000, 128, 585937, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('spmm_csr', None, 0, False, True)),
+    ('density-1panel-9', 100000, 3000, 128, 659180, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('tiled', 'float32', 0, False, False)),
+    ('density-B32767-per5', 100000, 32767, 128, 3999878, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('spmm_csr', None, 0, False, True)),
+    ('density-B32767-per8', 100000, 32767, 128, 6399805, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('spmm_csr', None, 0, False, True)),
+    ('density-B32768-per5', 100000, 32768, 128, 4000000, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('tiled', 'float32', 0, False, False)),
+    ('density-B32768-per8', 100000, 32768, 128, 6400000, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('tiled', 'float32', 0, False, False)),
+    ('density-narrow-12', 100000, 3000, 64, 878907, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('tiled', 'float32', 0, False, False)),
+    ('density-narrow-11', 70000, 3000, 64, 602418, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('spmm_csr', None, 0, False, True)),
+    ('b32bit-K1048063', 8192, 1048063, 1024, 12576756, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('tiled', 'float32', 0, False, False)),
+    ('b32bit-K1048064', 8192, 1048064, 1024, 12576768, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('spmm_csr', None, 0, False, True)),
+    ('disagree-M6000-wideN-K600', 6000, 600, 4096, 8790, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('spmm_csr', None, 0, False, True)),
+    ('disagree-M6000-wideN-K640', 6000, 640, 4096, 9375, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('tiled', 'float32', 0, False, False)),
+    ('disagree-N33-K600', 300000, 600, 33, 571290, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('spmm_csr', None, 0, False, True)),
+    ('disagree-f64xf32-N16-K600', 70000, 600, 16, 133301, 'float64', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('tiled', 'float64', 0, False, False)),
+    ('disagree-f64xf32-N30-K600', 70000, 600, 30, 133301, 'float64', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('tiled', 'float64', 0, False, False)),
+    ('disagree-f32xf64-N16-K600', 70000, 600, 16, 133301, 'float32', 'float64', 'csr', (), 0, _A, _A2, 'auto', False, True, None, ('spmm_csr', None, 0, False, True)),
+    ('coo-nnz19999999-uses0', 1000000, 5000, 128, 19999999, 'float32', 'float32', 'coo', (), 0, _A, _A2, 'auto', False, True, None, ('spmm_csr', None, 0, True, False)),
+    ('coo-nnz19999999-uses1', 1000000, 5000, 128, 19999999, 'float32', 'float32', 'coo', (), 1, _A, _A2, 'auto', False, True, None, ('tiled', 'float32', 0, True, False)),
+    ('coo-nnz20000000-uses0', 1000000, 5000, 128, 20000000, 'float32', 'float32', 'coo', (), 0, _A, _A2, 'auto', False, True, None, ('tiled', 'float32', 0, True, False)),
+    ('coo-nnz20000000-uses1', 1000000, 5000, 128, 20000000, 'float32', 'float32', 'coo', (), 1, _A, _A2, 'auto', False, True, None, ('tiled', 'float32', 0, True, False)),
+    ('coo-cached', 1000000, 5000, 128, 19999999, 'float32', 'float32', 'coo', ('float32',), 0, _A, _A2, 'auto', False, True, None, ('tiled', 'float32', 0, False, False)),
+    ('coo-wide-first', 100000, 3000, 1024, 4000000, 'float32', 'float32', 'coo', (), 0, _A, _A2, 'auto', False, True, None, ('tiled', 'float32', 0, True, False)),
+    ('coo-N8', 1000000, 5000, 8, 19999999, 'float32', 'float32', 'coo', (), 0, _A, _A2, 'auto', False, True, None, ('stream', None, 2, False, True)),
+    ('coo-ineligible', 1000, 3000, 128, 30000, 'float32', 'float32', 'coo', (), 0, _A, _A2, 'auto', False, True, None, ('spmm_csr', None, 0, False, True)),
+    ('csc-nnz199999-cached0', 50000, 1000, 128, 199999, 'float32', 'float32', 'csc', (), 0, _A, _A2, 'auto', False, True, None, ('tiled', 'float32', 0, False, False)),
+    ('csc-nnz199999-cached1', 50000, 1000, 128, 199999, 'float32', 'float32', 'csc', ('float32',), 0, _A, _A2, 'auto', False, True, None, ('tiled_csc', 'float32', 0, False, False)),
+    ('csc-nnz200000-cached0', 50000, 1000, 128, 200000, 'float32', 'float32', 'csc', (), 0, _A, _A2, 'auto', False, True, None, ('tiled_csc', 'float32', 0, False, False)),
+    ('csc-nnz200000-cached1', 50000, 1000, 128, 200000, 'float32', 'float32', 'csc', ('float32',), 0, _A, _A2, 'auto', False, True, None, ('tiled_csc', 'float32', 0, False, False)),
+    ('csc-f64-N8', 70000, 3000, 8, 2100000, 'float64', 'float64', 'csc', (), 0, _A, _A2, 'auto', False, True, None, ('tiled_csc', 'float64', 0, False, False)),
+    ('csc-small-N8', 70000, 3000, 8, 199999, 'float32', 'float32', 'csc', (), 0, _A, _A2, 'auto', False, True, None, ('stream', None, 2, False, True)),
+    ('hub-nnz16383', 200000, 50000, 128, 16383, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, (5000, 1), ('spmm_csr', None, 0, False, True)),
+    ('hub-nnz16384', 200000, 50000, 128, 16384, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, (5000, 1), ('hub',)),
+    ('hub-longest4095', 200000, 50000, 128, 100000, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, (4095, 1), ('spmm_csr', None, 0, False, True)),
+    ('hub-longest4096', 200000, 50000, 128, 100000, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, (4096, 1), ('hub',)),
+    ('hub-hot1024', 200000, 50000, 128, 10000000, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, (5000, 1024), ('hub',)),
+    ('hub-hot1025', 200000, 50000, 128, 10000000, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, (5000, 1025), ('spmm_csr', None, 0, False, True)),
+    ('hub-stream-longest32767', 200000, 3000, 4, 2000000, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, (32767, 1), ('stream', None, 1, False, True)),
+    ('hub-stream-N8-longest32767', 200000, 3000, 8, 2000000, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, (32767, 1), ('stream', None, 2, False, True)),
+    ('hub-stream-longest32768', 200000, 3000, 4, 2000000, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, (32768, 1), ('hub',)),
+    ('hub-stream-N8-longest32768', 200000, 3000, 8, 2000000, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, (32768, 1), ('hub',)),
+    ('hub-no-stream-N8-longest5000', 200000, 3000, 8, 2000000, 'float32', 'float32', 'csr', (), 0, _MIS, _A2, 'auto', False, True, (5000, 1), ('hub',)),
+    ('hub-exact', 200000, 50000, 128, 100000, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', True, True, (5000, 1), ('spmm_csr', None, 0, False, True)),
+    ('hub-off', 200000, 50000, 128, 100000, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, False, (5000, 1), ('spmm_csr', None, 0, False, True)),
+    ('hub-i64', 200000, 50000, 128, 100000, 'int64', 'int64', 'csr', (), 0, _A, _A2, 'auto', False, True, (5000, 1), ('hub',)),
+    ('hub-tiled-operand', 70000, 3000, 128, 2666016, 'float32', 'float32', 'csr', (), 0, _A, _A2, 'auto', False, True, (40000, 3), ('hub',)),
+    ('hub-csc-direct', 70000, 3000, 128, 2666016, 'float32', 'float32', 'csc', (), 0, _A, _A2, 'auto', False, True, (40000, 3), ('tiled_csc', 'float32', 0, False, False)),
+    ('hub-csc-small', 5000, 3000, 8, 100000, 'float32', 'float32', 'csc', (), 0, _A, _A2, 'auto', False, True, (5000, 2), ('hub',)),
+    ('hub-coo', 200000, 50000, 128, 100000, 'float32', 'float32', 'coo', (), 0, _A, _A2, 'auto', False, True, (5000, 1), ('hub',)),
+]
+
+
+@pytest.mark.parametrize("case", _SPMM_ROUTES, ids=[c[0] for c in _SPMM_ROUTES])
+def test_spmm_route_table(hiplib, case):
+    """`_dot._spmm_route`, the one choice of kernel for `sparse @ dense`: hub-row split, the executor (from the CSR arrays or
+    from a csc operand's own), the stream kernel in 1-3 passes, or what `spamd_spmm_csr` picks; whether a COO counts the
+    product and whether a `_SpmmPlan` is kept.  `prepare_operand` builds a block stream only for a route with an executor
+    value type (`dt`): not for the 5-12-column products the stream kernel takes."""
+    import torch
+
+    from sparse_amd import _dot as D
+
+    _, M, Kd, N, nnz, vd, bd, form, cached, uses, dptr, iptr, tiled, exact, hot, finding, want = case
+    r = D._spmm_route(M, Kd, N, nnz, getattr(torch, vd), getattr(torch, bd), form, tuple(getattr(torch, c) for c in cached), uses,
+                      dptr, iptr, tiled, exact, hot)
+    # `_hot_row_split` makes a split when the longest row reaches HOT_ROW_MIN elements and at most HOT_ROWS_MAX rows do
+    split = None
+    if finding is not None and finding[0] >= D.HOT_ROW_MIN and finding[1] <= D.HOT_ROWS_MAX:
+        split = (None,) * 5 + (finding[0],)
+    got = ("hub",) if r.takes_hub(split) else (r.kind, None if r.dt is None else str(r.dt).replace("torch.", ""), r.passes,
+                                               r.count, r.plan)
+    assert got == want
+
+
+def test_ldsb_bound_is_the_librarys(hiplib):
+    """`_dot.LDSB_MAX_K`, the executor's "short contracted axis" bound, is the K limit of `spamd_spmm_csr_ldsb_fits`"""
+    from sparse_amd import _dot as D
+
+    for code in (0, 1, 2, 3):    # F32, F64, I32, I64
+        assert hiplib.spamd_spmm_csr_ldsb_fits(code, 8192, D.LDSB_MAX_K, 32, 1 << 20, 32, 2 << 20, 32) == 1
+        assert hiplib.spamd_spmm_csr_ldsb_fits(code, 8192, D.LDSB_MAX_K + 1, 32, 1 << 20, 32, 2 << 20, 32) == 0

@@ -256,16 +256,17 @@ def test_reduction_drops_results_equal_to_the_fill_value_in_one_read(sp):
 
 @pytest.mark.parametrize("dtype, N", [(np.float32, 5), (np.float32, 6), (np.float32, 7), (np.float32, 9), (np.float32, 127), (np.float32, 129), (np.float32, 255), (np.float32, 32), (np.float32, 48), (np.float32, 160), (np.float32, 34), (np.float32, 33),
                                       (np.float64, 16), (np.float64, 80), (np.float64, 17)])
-def test_narrow_results_through_the_executor(sp, dtype, N, monkeypatch):
+def test_narrow_results_through_the_forced_executor(sp, dtype, N, monkeypatch):
     """Results narrower than a whole number of column panels: B is zero-padded to whole panels, C is not - the last panel
     stores its leading columns only (odd float32 widths: the straddling lane stores one column).  Bit-identical to the
     row-group kernel (same k-ascending FMA per output element), the memory just past the result untouched.
-    (Round 6: results of 5-12 columns from CSR arrays take the stream kernel in several passes - switched off here: the
-    executor still serves these widths for CSC operands without a CSR twin and for B too large for the LDS.)"""
+    (Round 6: results of 5-12 columns from CSR arrays take the stream kernel in several passes - switched off here, through
+    the route's stream query: the executor still serves these widths for CSC operands without a CSR twin and for B too large
+    for the LDS.)"""
     from bench import make_csr_device
     from sparse_amd import _dot, _kernels
 
-    monkeypatch.setattr(_kernels, "STREAM_MULTI_MAX_N", 4)
+    monkeypatch.setattr(_kernels, "stream_passes", lambda *args: 0)
 
     M, K = 70_000, 3000
     tdt = torch.float32 if dtype == np.float32 else torch.float64
