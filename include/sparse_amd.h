@@ -33,6 +33,9 @@ extern "C" {
 #define SPAMD_I64 3
 #define SPAMD_BF16 4
 #define SPAMD_U8 5 /* bool (0/1) — results of comparisons, any/all, astype(bool) */
+#define SPAMD_C64 6  /* complex64: interleaved (re, im) float32 pairs - products only (spamd_spmm_csr_complex, spamd_spgemm_expand,
+                      * spamd_segment_reduce with op = add) */
+#define SPAMD_C128 7 /* complex128: interleaved (re, im) float64 pairs - the same entry points */
 
 #define SPAMD_MAX_NDIM 16 /* largest array rank the key kernels accept */
 
@@ -78,6 +81,22 @@ int spamd_spmm_csr(int val_dtype, int idx_dtype, int64_t M, int64_t K, int64_t N
                    const void* a_data, const void* a_indices, const void* a_indptr,
                    const void* b, int64_t ldb, void* out, int64_t ldo,
                    unsigned flags, void* stream);
+
+/* The same product for COMPLEX values (csrc/spmm_complex.hip): val_dtype C64 | C128, values stored as interleaved (re, im)
+ * pairs as NumPy and torch store them; ldb / ldo count complex elements; a_data, b and out are at least 8-byte aligned
+ * (SPAMD_EINVAL otherwise).  Same contract as spamd_spmm_csr: every out element is written once, by one lane, summed in
+ * storage order.  One term is  re += ar*br - ai*bi; im += ar*bi + ai*br : four fused multiply-adds by default; with
+ * SPAMD_EXACT_MULADD four rounded products, a rounded subtraction and a rounded addition, then the rounded accumulate -
+ * NumPy's scalar complex multiply and add, bit-identical to the reference loop.  A lane reads 16 bytes of a B row per
+ * access (one complex128 column, two complex64 columns) when b and out are 16-byte aligned (complex64: and N, ldb, ldo
+ * even; complex128: and a_data), else 8 bytes.  Results of at most 4 complex64 / 2 complex128 columns without
+ * SPAMD_EXACT_MULADD or SPAMD_SPMM_ROWGROUP take the row-vector form (lanes along a row, a butterfly: a fixed tree
+ * order per row, deterministic).  The LDS-resident-B, stream, inspector/executor and hub-row forms are real-only.
+ * idx_dtype: I32 | I64.  Other codes: SPAMD_ETYPE. */
+int spamd_spmm_csr_complex(int val_dtype, int idx_dtype, int64_t M, int64_t K, int64_t N,
+                           const void* a_data, const void* a_indices, const void* a_indptr,
+                           const void* b, int64_t ldb, void* out, int64_t ldo,
+                           unsigned flags, void* stream);
 
 /* The same product with B RESIDENT IN LDS, for a short contracted axis (`_dot_csr_ndarray` / `_dot_coo_ndarray` as
  * tensordot uses them, `_common.py:720-755, 979-1014`; BASELINE config 3: K = 512): a 256-byte column panel of B —
@@ -387,6 +406,7 @@ int spamd_merge_union_fused(int op, int val_dtype, int64_t na, const int64_t* ka
  *   Short runs: one thread per run, strictly left to right (bit-identical to reduceat).
  *   Long runs (n/nseg >= 24 and seg_start_ws != NULL, nseg+1 int64): one wave per run (tree order).
  *   op: 0 add 1 multiply 2 maximum 3 minimum 4 logical_or 5 logical_and 6 fmax 7 fmin (NaN-skipping).
+ *   val_dtype C64 | C128: op add only (SPAMD_EINVAL otherwise), always one thread per run, left to right.
  * ------------------------------------------------------------------------------------- */
 int spamd_segment_reduce(int op, int val_dtype, int64_t n, const void* data, const int64_t* heads,
                          const int64_t* offsets, int64_t nseg, void* out, int64_t* counts,
@@ -456,6 +476,8 @@ int spamd_hot_rows_combine(int val_dtype, int64_t n_hot, int64_t n_cols, const v
  *   (2) keys[t] = a_rows[p]*n_col + b_col, vals[t] = a*b for every product t in [0, P).
  *   A stable sort by key + spamd_segment_reduce(add) then gives every output element summed in
  *   the reference's order (bit-identical), with rows sorted by column.
+ *   val_dtype of (2): F32 | F64 | I32 | I64 | C64 | C128; a complex product is the four rounded products, the rounded
+ *   subtraction and the rounded addition of NumPy's scalar multiply (never contracted).
  * ------------------------------------------------------------------------------------- */
 int spamd_spgemm_count(int idx_dtype, int64_t p0, int64_t np, const void* a_indices, const void* b_indptr,
                        int64_t* cnt, void* stream);

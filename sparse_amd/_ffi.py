@@ -14,6 +14,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sparse_amd.h")
 
 # dtype codes (include/sparse_amd.h)
 F32, F64, I32, I64, BF16, U8 = 0, 1, 2, 3, 4, 5
+C64, C128 = 6, 7     # complex products only: spamd_spmm_csr_complex, spamd_spgemm_expand, spamd_segment_reduce(add)
 MAX_NDIM = 16
 EXACT_MULADD = 1
 TILED_GROUP_ENDS = 2
@@ -147,6 +148,7 @@ SIGNATURES = {
     "spamd_has_nan": (_int, [_int, _i64, _vp, _vp, _vp]),
     "spamd_has_nan_async": (_int, [_int, _i64, _vp, _vp, _vp]),
     "spamd_spmm_csr": (_int, [_int, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _u32, _vp]),
+    "spamd_spmm_csr_complex": (_int, [_int, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _u32, _vp]),
     "spamd_spmm_csr_ldsb": (_int, [_int, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _u32, _vp]),
     "spamd_deliver_words": (_int, [_vp, _int, _vp, _i64, _vp]),
     "spamd_transpose_2d": (_int, [_int, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),

@@ -21,6 +21,23 @@ def dot_dtype(dt1, dt2):
     return (np.zeros((), dtype=np_dtype(dt1)) * np.zeros((), dtype=np_dtype(dt2))).dtype
 
 
+_COMPLEX_CODE = {torch.complex64: _ffi.C64, torch.complex128: _ffi.C128}
+
+
+def product_code(dt):
+    """C-ABI value code of a PRODUCT's result type: what `code_of` knows plus complex64 / complex128, which only the
+    product kernels take (`spamd_spmm_csr_complex`, `spamd_spgemm_expand`, `spamd_segment_reduce` with add).  Kept apart
+    from `code_of`, whose TypeError is the "no device kernel for this dtype" probe of the elementwise and reduction layers."""
+    dt = torch_dtype(dt)
+    code = _COMPLEX_CODE.get(dt)
+    return code_of(dt) if code is None else code
+
+
+def _as_reals(t):
+    """A complex tensor as its interleaved (re, im) reals, flat (a view); anything else unchanged."""
+    return torch.view_as_real(t).reshape(-1) if t.is_complex() else t
+
+
 def _unify_index(*idx):
     """Index arrays handed to one kernel share a width: int32 only if all are int32."""
     want = torch.int32 if all(i.dtype == torch.int32 for i in idx) else torch.int64
@@ -48,7 +65,7 @@ def dot_csr_ndarray(out_shape, a_data, a_indices, a_indptr, b, *, exact=False, o
     M, N = int(out_shape[0]), int(out_shape[1])
     dev = require_hip(a_data, a_indices, a_indptr, b)
     dtr = torch_dtype(dot_dtype(a_data.dtype, b.dtype))
-    vcode = code_of(dtr)
+    vcode = product_code(dtr)
     if a_data.dtype != dtr:
         a_data = a_data.to(dtr)
     if b.dtype != dtr:
@@ -66,6 +83,12 @@ def dot_csr_ndarray(out_shape, a_data, a_indices, a_indptr, b, *, exact=False, o
     elif out.shape != (M, N) or out.dtype != dtr or not out.is_contiguous():
         raise ValueError("out buffer has wrong shape/dtype/layout")
     flags = (_ffi.EXACT_MULADD if exact else 0) | (_ffi.SPMM_ROWGROUP if keep_order else 0) | (_ffi.SPMM_ROWVEC if rowvec else 0)
+    if dtr.is_complex:
+        # csrc/spmm_complex.hip: the row-group and row-vector kernels for (re, im) pairs; the LDS-resident-B, stream and
+        # executor forms are real-only (mixed real x complex operands were promoted above, like the reference's `v * b[k, j]`)
+        _ffi.call("spamd_spmm_csr_complex", vcode, code_of(it), M, K, N, ptr(a_data), ptr(a_indices), ptr(a_indptr),
+                  ptr(b), max(N, 1), ptr(out), max(N, 1), flags & ~_ffi.SPMM_ROWVEC, stream_ptr(dev))
+        return out
     if stream_passes(M, K, N, dtr, a_data, a_indices, flags):
         # what spamd_spmm_csr's own dispatch would pick, with the number of stored elements handed over (the kernel need
         # not read it from indptr at the head of every wave's start-up chain)
@@ -94,9 +117,9 @@ def has_nan(data):
     """Any NaN in a float tensor?  (reference `nan_check`, _common.py:51-69).  One streaming
     pass on the device; the 4-byte flag is the only thing copied back."""
     dev = require_hip(data)
-    if data.numel() == 0 or not data.is_floating_point():
+    if data.numel() == 0 or not (data.is_floating_point() or data.is_complex()):
         return False
-    data = data.contiguous()
+    data = _as_reals(data.contiguous())     # a complex buffer is scanned as twice as many reals
     if data.data_ptr() % 16:
         data = data.clone()
     flag = torch.empty(1, dtype=torch.int32, device=dev)
@@ -236,9 +259,9 @@ class NanProbe:
 
 def has_nan_async(data):
     """`has_nan` without draining the stream: returns a NanProbe (or False when `data` cannot hold a NaN)."""
-    if data.numel() == 0 or not data.is_floating_point():
+    if data.numel() == 0 or not (data.is_floating_point() or data.is_complex()):
         return False
-    data = data.contiguous()
+    data = _as_reals(data.contiguous())     # a complex buffer is scanned as twice as many reals
     if data.data_ptr() % 16:
         data = data.clone()
     return NanProbe(data)
@@ -728,7 +751,9 @@ def _sparsify(dense, struct_mask=None, numeric=False):
         fused = dense_nonfill(flat, 0, numeric=numeric)
         if fused is not None:
             return fused
-    if numeric:
+    if numeric and flat.is_complex():
+        flags = _complex_nonzero_flags(flat)
+    elif numeric:
         from ._umath import binary_arrays
 
         nz = binary_arrays("not_equal", flat, torch.zeros(1, dtype=flat.dtype, device=flat.device), b_scalar=True)
@@ -748,13 +773,27 @@ def _sparsify(dense, struct_mask=None, numeric=False):
     return compact(iota, flags, offs, cnt), compact(flat, flags, offs, cnt)
 
 
+def _complex_nonzero_flags(flat):
+    """int64 flags [n + 1] of a flat complex tensor: 1 where the value != 0, i.e. where either part is (+0 and -0 are both
+    zero, NaN is not) - the real comparison over the (re, im) reals, then each pair of result bytes tested as one 16-bit word."""
+    from ._umath import binary_arrays
+
+    reals = _as_reals(flat.contiguous())
+    nz = binary_arrays("not_equal", reals, torch.zeros(1, dtype=reals.dtype, device=reals.device), b_scalar=True,
+                       out_bool_as=torch.uint8)
+    return flag_ne_bits(nz.view(torch.int16), 0)
+
+
 def _pattern_product(out_shape, a_indices, a_indptr, b, csc_shape=None):
     """Structural non-zero test of the reference's sparse-returning variants: entry (i, j) is
     stored iff some b[k, j] != 0 with k in row i of A (_common.py:796-798, 843-844)."""
     from ._umath import binary_arrays
 
-    bz = binary_arrays("not_equal", b.reshape(-1).contiguous(), torch.zeros(1, dtype=b.dtype, device=b.device),
-                       b_scalar=True)
+    if b.is_complex():
+        bz = _complex_nonzero_flags(b.reshape(-1))[:b.numel()]
+    else:
+        bz = binary_arrays("not_equal", b.reshape(-1).contiguous(), torch.zeros(1, dtype=b.dtype, device=b.device),
+                           b_scalar=True)
     bz = convert(bz, torch.float32).reshape(b.shape)
     ones = torch.ones(a_indices.numel(), dtype=torch.float32, device=b.device)
     if csc_shape is None:
@@ -811,7 +850,7 @@ def _spgemm_keys(n_row, n_col, a_data, a_indices, a_rows, b_data, b_indices, b_i
 
     dev = require_hip(a_data, b_data)
     dtr = torch_dtype(dot_dtype(a_data.dtype, b_data.dtype))
-    vcode = code_of(dtr)
+    vcode = product_code(dtr)
     a_data = a_data.to(dtr).contiguous() if a_data.dtype != dtr else a_data.contiguous()
     b_data = b_data.to(dtr).contiguous() if b_data.dtype != dtr else b_data.contiguous()
     (a_indices, b_indices, b_indptr), it = _unify_index(a_indices.contiguous(), b_indices.contiguous(),
@@ -846,7 +885,11 @@ def _spgemm_keys(n_row, n_col, a_data, a_indices, a_rows, b_data, b_indices, b_i
             vals = torch.empty(P, dtype=dtr, device=dev)
             _ffi.call("spamd_spgemm_expand", vcode, code_of(it), p, q - p, ptr(a_data), ptr(a_indices), ptr(a_rows),
                       ptr(b_data), ptr(b_indices), ptr(b_indptr), ptr(offs), P, n_col, ptr(keys), ptr(vals), s)
-            keys, vals = sort_key_value(keys, vals, max(n_row * n_col - 1, 1))
+            if vals.element_size() > 8:     # complex128: the pair sort moves 4- and 8-byte values; sort a permutation, gather
+                keys, perm = sort_keys(keys, max(n_row * n_col - 1, 1))
+                vals = gather(vals, perm)
+            else:
+                keys, vals = sort_key_value(keys, vals, max(n_row * n_col - 1, 1))
             heads = flag_heads(keys)
             ho = exclusive_scan(heads)
             c = int(ho[-1])
@@ -1027,6 +1070,8 @@ def _spgemm_rows(n_row, n_col, a_data, a_indices, a_indptr, b_data, b_indices, b
             return res
     dev = require_hip(a_data, b_data)
     dtr = torch_dtype(dot_dtype(a_data.dtype, b_data.dtype))
+    if dtr.is_complex:
+        return None     # the row-local, small and bitmap kernels are real-only: the global expand-sort-compress has complex values
     vcode = code_of(dtr)
     if n_col >= 2 ** 31 - 1 or n_row == 0:
         return None

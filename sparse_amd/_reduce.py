@@ -33,7 +33,10 @@ def segment_reduce(data, heads, offs, count, op, want_counts=False, sequential=F
     counts = torch.empty(count, dtype=torch.int64, device=dev) if want_counts else None
     ws = (torch.empty(count + 1, dtype=torch.int64, device=dev)
           if (count and n // max(count, 1) >= 24 and not sequential) else None)
-    code = _ffi.U8 if data.dtype == torch.uint8 else code_of(data.dtype)
+    if data.is_complex() and op == "add" and sequential and not want_counts:
+        code = K.product_code(data.dtype)   # sums of complex products (sparse x sparse): this kernel's one complex case
+    else:
+        code = _ffi.U8 if data.dtype == torch.uint8 else code_of(data.dtype)
     _ffi.call("spamd_segment_reduce", _RED_OPS[op], code, n, ptr(data.contiguous()), ptr(heads), ptr(offs), count,
               ptr(out), ptr(counts), ptr(ws), stream_ptr(dev))
     if was_bool:

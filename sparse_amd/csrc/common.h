@@ -108,6 +108,25 @@ __device__ __forceinline__ T mul_add(T a, T b, T c) {
   }
 }
 
+// A complex value as NumPy and torch store it: (re, im) of R = float / double, with the arithmetic of NumPy's SCALAR complex
+// multiply and add - four rounded products, a rounded subtraction and a rounded addition; componentwise sums - which the
+// reference's interpreted loops perform (SPAMD_C64 / SPAMD_C128; never contracted: the pragma holds whatever the flags).
+template <typename R>
+struct alignas(8) Cplx {
+  R re, im;
+};
+template <typename R>
+__host__ __device__ __forceinline__ Cplx<R> operator*(Cplx<R> a, Cplx<R> b) {
+#pragma clang fp contract(off)
+  const R p1 = a.re * b.re, p2 = a.im * b.im, p3 = a.re * b.im, p4 = a.im * b.re;
+  return Cplx<R>{p1 - p2, p3 + p4};
+}
+template <typename R>
+__host__ __device__ __forceinline__ Cplx<R> operator+(Cplx<R> a, Cplx<R> b) {
+#pragma clang fp contract(off)
+  return Cplx<R>{a.re + b.re, a.im + b.im};
+}
+
 template <typename T, int N>
 struct alignas(sizeof(T) * N) Vec {
   T v[N];

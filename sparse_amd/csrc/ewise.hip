@@ -364,6 +364,22 @@ __global__ void __launch_bounds__(256) segreduce_thread_kernel(int op, const T* 
   }
 }
 
+// the same for complex values, op = add only (`sums[k] += ...` of the reference's sparse x sparse loops)
+template <typename R>
+__global__ void __launch_bounds__(256) segadd_complex_thread_kernel(const Cplx<R>* __restrict__ data, int64_t n,
+                                                                    const int64_t* __restrict__ heads,
+                                                                    const int64_t* __restrict__ offs,
+                                                                    Cplx<R>* __restrict__ out, int64_t* __restrict__ counts) {
+  GRID_STRIDE(i, n) {
+    if (!heads[i]) continue;
+    Cplx<R> acc = data[i];
+    int64_t j = i + 1;
+    for (; j < n && !heads[j]; ++j) acc = acc + data[j];
+    out[offs[i]] = acc;
+    if (counts) counts[offs[i]] = j - i;
+  }
+}
+
 // segment starts given explicitly (seg_start[g], g in [0, nseg], seg_start[nseg] = n): one wave per run
 template <typename T>
 __global__ void __launch_bounds__(256) segreduce_wave_kernel(int op, const T* __restrict__ data,
@@ -628,6 +644,17 @@ extern "C" int spamd_segment_reduce(int op, int val_dtype, int64_t n, const void
   if (n < 0 || nseg < 0) return SPAMD_EINVAL;
   if (n == 0 || nseg == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
+  if (val_dtype == SPAMD_C64 || val_dtype == SPAMD_C128) {
+    // complex sums (the products of sparse x sparse): one thread per run, strictly left to right
+    if (op != R_ADD) return SPAMD_EINVAL;
+    if (val_dtype == SPAMD_C64)
+      hipLaunchKernelGGL(segadd_complex_thread_kernel<float>, dim3(grid_for(n)), dim3(256), 0, s, (const Cplx<float>*)data, n,
+                         heads, offsets, (Cplx<float>*)out, counts);
+    else
+      hipLaunchKernelGGL(segadd_complex_thread_kernel<double>, dim3(grid_for(n)), dim3(256), 0, s, (const Cplx<double>*)data, n,
+                         heads, offsets, (Cplx<double>*)out, counts);
+    return launch_status();
+  }
   const bool long_runs = seg_start_ws != nullptr && (n / nseg) >= 24;
   VAL_SWITCH5(val_dtype, T, {
     if (long_runs) {

@@ -78,6 +78,18 @@ extern "C" int spamd_spgemm_expand(int val_dtype, int idx_dtype, int64_t p0, int
                                    int64_t n_col, int64_t* keys, void* vals, void* stream) {
   if (np < 0 || P < 0 || n_col < 0) return SPAMD_EINVAL;
   if (P == 0 || np == 0) return 0;
+#define SPAMD_EXPAND_COMPLEX(CODE, R)                                                                                   \
+  if (val_dtype == CODE) {                                                                                              \
+    using T = Cplx<R>;                                                                                                  \
+    SPAMD_DISPATCH_IDX(idx_dtype, I, hipLaunchKernelGGL((spgemm_expand_kernel<T, I>), dim3(grid_for(P)), dim3(256), 0,  \
+                                                        (hipStream_t)stream, (const T*)a_data, (const I*)a_indices,     \
+                                                        a_rows, p0, np, (const T*)b_data, (const I*)b_indices,          \
+                                                        (const I*)b_indptr, offsets, P, n_col, keys, (T*)vals))         \
+    return launch_status();                                                                                             \
+  }
+  SPAMD_EXPAND_COMPLEX(SPAMD_C64, float)
+  SPAMD_EXPAND_COMPLEX(SPAMD_C128, double)
+#undef SPAMD_EXPAND_COMPLEX
   SPAMD_DISPATCH_VAL(val_dtype, T, {
     SPAMD_DISPATCH_IDX(idx_dtype, I, hipLaunchKernelGGL((spgemm_expand_kernel<T, I>), dim3(grid_for(P)), dim3(256), 0,
                                                         (hipStream_t)stream, (const T*)a_data, (const I*)a_indices,
