@@ -33,8 +33,9 @@ extern "C" {
 #define SPAMD_I64 3
 #define SPAMD_BF16 4
 #define SPAMD_U8 5 /* bool (0/1) — results of comparisons, any/all, astype(bool) */
-#define SPAMD_C64 6  /* complex64: interleaved (re, im) float32 pairs - products only (spamd_spmm_csr_complex, spamd_spgemm_expand,
-                      * spamd_segment_reduce with op = add) */
+#define SPAMD_C64 6  /* complex64: interleaved (re, im) float32 pairs - the products (spamd_spmm_csr_complex, spamd_spgemm_expand,
+                      * spamd_segment_reduce with op = add) and the complex elementwise / reduction entry points (spamd_cplx_*,
+                      * spamd_merge_union_complex) */
 #define SPAMD_C128 7 /* complex128: interleaved (re, im) float64 pairs - the same entry points */
 
 #define SPAMD_MAX_NDIM 16 /* largest array rank the key kernels accept */
@@ -365,7 +366,7 @@ int spamd_ewise_binary(int op, int val_dtype, int64_t n, const void* a, int a_is
  *   21 reciprocal 22 positive 23 log2 24 log10 25 exp2 26 arcsinh 27 arctanh 28 cbrt 29 deg2rad
  *   30 rad2deg (out dtype = val_dtype); 64 isnan 65 isinf 66 isfinite 67 logical_not 68 signbit (out U8) */
 int spamd_ewise_unary(int op, int val_dtype, int64_t n, const void* a, void* out, void* stream);
-/* out[i] = mask[i] ? a[i] : b[i] (`np.where` on aligned arrays of 1-, 4- or 8-byte elements, moved bit-wise; mask = 0/1 bytes;
+/* out[i] = mask[i] ? a[i] : b[i] (`np.where` on aligned arrays of 1-, 4-, 8- or 16-byte elements, moved bit-wise; mask = 0/1 bytes;
  * *_is_scalar broadcasts a 1-element device array) */
 int spamd_ewise_select(int elem_bytes, int64_t n, const void* mask_u8, const void* a, int a_is_scalar, const void* b,
                        int b_is_scalar, void* out, void* stream);
@@ -635,6 +636,59 @@ int spamd_sddmm_mfma_tiles(int idx_dtype, int64_t ntiles, const int64_t* tiles, 
                            const int64_t* keys_sorted, const int64_t* perm, int64_t tile_cols, int64_t M, int64_t N,
                            const void* rows, const void* cols, const float* s_data, const void* A, int64_t lda,
                            const void* Bt, int64_t ldb, int64_t K, float* out, void* stream);
+
+/* =======================================================================================
+ * A11  Complex elementwise functions, conversions and reductions (val_dtype C64 | C128; SPAMD_ETYPE otherwise)
+ *   The formulas are NumPy's own loops, statement for statement, so that results are bit-identical to the reference's
+ *   (which applies the ufunc to matched value arrays, sparse/numba_backend/_umath.py:420-470):
+ *     multiply  re = fma(ar, br, -(ai * bi)), im = fma(ar, bi, ai * br), inner products rounded (NumPy's ARRAY loop
+ *               fuses; the products of spamd_spmm_csr_complex / spamd_spgemm_expand are the unfused SCALAR product);
+ *               square is the same with b = a
+ *     divide    Smith's form, unfused: if |br| >= |bi|: both zero -> (ar / |br|, ai / |bi|); else rat = bi / br,
+ *               scl = 1 / (br + bi * rat), re = (ar + ai * rat) * scl, im = (ai - ar * rat) * scl; otherwise rat = br / bi,
+ *               scl = 1 / (bi + br * rat), re = (ar * rat + ai) * scl, im = (ai * rat - ar) * scl
+ *     abs       hypot(re, im) of the device library (spamd_ewise_binary's op 13): within 4 ulp, the only inexact op
+ *     others    componentwise; isnan / isinf: either part, isfinite: both; equal: both parts equal
+ *   Arrays need 8-byte alignment; where every array of a call is 16-byte aligned each lane moves 16 bytes per access.
+ * ------------------------------------------------------------------------------------- */
+/* out[i] = a[i] (op) b[i]; *_is_scalar broadcasts a 1-element device array.  op: 0 add 1 subtract 2 multiply 3 divide
+ * (out: val_dtype); 36 equal 37 not_equal (out: U8).  Any other op (power, ordered comparisons, maximum, logical_*, ...):
+ * SPAMD_EINVAL - those functions of complex values are not device functions. */
+int spamd_cplx_binary(int op, int val_dtype, int64_t n, const void* a, int a_is_scalar, const void* b, int b_is_scalar,
+                      void* out, void* stream);
+/* out[i] = f(a[i]); op: 0 negative 20 square 22 positive 96 conjugate (out: val_dtype); 1 absolute 97 real 98 imag (out: F32
+ * for C64, F64 for C128); 64 isnan 65 isinf 66 isfinite (out: U8).  Any other op: SPAMD_EINVAL. */
+int spamd_cplx_unary(int op, int val_dtype, int64_t n, const void* a, void* out, void* stream);
+/* astype to complex: src_dtype F32 | F64 | I32 | I64 | U8 (imaginary part 0) or C64 | C128 (each part converted);
+ * dst_dtype C64 | C128. */
+int spamd_cplx_convert(int src_dtype, int dst_dtype, int64_t n, const void* src, void* dst, void* stream);
+/* out[i] = (re, im), rounded to float32 parts for C64 */
+int spamd_cplx_fill(int val_dtype, int64_t n, void* out, double re, double im, void* stream);
+/* The fused merge-path union (spamd_merge_union with fill = 2) for complex values: tiles cut by spamd_merge_partition,
+ * counts = spamd_merge_num_blocks(na, nb) + 2 int64 of workspace (zeroed here), counts[nblocks + 1] receives the number of
+ * outputs, out_keys / out_vals hold na + nb elements.  op as spamd_cplx_binary.  The fill values are passed by HOST
+ * address: fill_a / fill_b point to one value of val_dtype, fill_out to one value of val_dtype (ops 0-3) or to one byte
+ * (ops 36, 37); results bit-identical to *fill_out (both parts) are dropped. */
+int spamd_merge_union_complex(int op, int val_dtype, int64_t na, const int64_t* ka, const void* va, int64_t nb,
+                              const int64_t* kb, const void* vb, const void* fill_a, const void* fill_b, const void* fill_out,
+                              const int64_t* part, int64_t* counts, int64_t* out_keys, void* out_vals, void* stream);
+/* Reduce the runs data[starts[g] .. starts[g + 1]) (starts: int64[nseg + 1], ascending; empty runs are not written), one
+ * thread per run, in the order of the reference's `ufunc.reduceat` (_coo/core.py:1660), bit for bit:
+ *   op 0 (add)       out[g] = x0 + P(x1 .. x(m-1)) per component, P = NumPy's pairwise sum over c complex values:
+ *                    c < 4: from -0.0, left to right; c <= 64: four accumulators a_j = x_j, a_j += x_(4t+j) over the whole
+ *                    groups of four, (a0 + a1) + (a2 + a3), then the remaining c mod 4 values left to right;
+ *                    c > 64: P(first c1) + P(the rest), c1 = (c - c mod 8) / 2
+ *   op 1 (multiply)  left to right with the unfused product (re = ar*br - ai*bi, im = ar*bi + ai*br)
+ * max_len > 0: runs longer than max_len are skipped (their out[g] is left alone: spamd_cplx_sum_long is for them).
+ * (spamd_segment_reduce with C64 / C128 stays the strictly-left-to-right sum of the sparse x sparse products.) */
+int spamd_cplx_segment_reduce(int op, int val_dtype, int64_t n, const void* data, const int64_t* starts, int64_t nseg,
+                              int64_t max_len, void* out, void* stream);
+/* One long run of m >= 2 values in the same order as op 0 above: the leaves of the tree (at most 64 values each) are
+ * summed by one thread each, the joins above them are done in the tree's own order, 8 levels per launch.  ws: workspace
+ * of spamd_cplx_sum_long_ws_bytes(m) bytes (SPAMD_EWS when smaller).  out: one value.  The result does not depend on the
+ * launch geometry. */
+int64_t spamd_cplx_sum_long_ws_bytes(int64_t m);
+int spamd_cplx_sum_long(int val_dtype, int64_t m, const void* run, void* out, void* ws, int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sparse_amd.h")
 
 # dtype codes (include/sparse_amd.h)
 F32, F64, I32, I64, BF16, U8 = 0, 1, 2, 3, 4, 5
-C64, C128 = 6, 7     # complex products only: spamd_spmm_csr_complex, spamd_spgemm_expand, spamd_segment_reduce(add)
+C64, C128 = 6, 7     # the complex products (spamd_spmm_csr_complex, spamd_spgemm_expand, spamd_segment_reduce(add)) and spamd_cplx_*
 MAX_NDIM = 16
 EXACT_MULADD = 1
 TILED_GROUP_ENDS = 2
@@ -153,6 +153,14 @@ SIGNATURES = {
     "spamd_deliver_words": (_int, [_vp, _int, _vp, _i64, _vp]),
     "spamd_transpose_2d": (_int, [_int, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     "spamd_spmm_csr_stream": (_int, [_int, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _u32, _vp]),
+    "spamd_cplx_binary": (_int, [_int, _int, _i64, _vp, _int, _vp, _int, _vp, _vp]),
+    "spamd_cplx_unary": (_int, [_int, _int, _i64, _vp, _vp, _vp]),
+    "spamd_cplx_convert": (_int, [_int, _int, _i64, _vp, _vp, _vp]),
+    "spamd_cplx_fill": (_int, [_int, _i64, _vp, _C.c_double, _C.c_double, _vp]),
+    "spamd_merge_union_complex": (_int, [_int, _int, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "spamd_cplx_segment_reduce": (_int, [_int, _int, _i64, _vp, _vp, _i64, _i64, _vp, _vp]),
+    "spamd_cplx_sum_long_ws_bytes": (_i64, [_i64]),
+    "spamd_cplx_sum_long": (_int, [_int, _i64, _vp, _vp, _vp, _i64, _vp]),
     "spamd_spmm_csr_stream_fits": (_int, [_int, _i64, _i64, _i64, _vp, _vp]),
     "spamd_spmm_csr_stream_passes": (_int, [_int, _i64, _i64, _i64, _vp, _vp, _u32]),
     "spamd_spmm_csr_ldsb_fits": (_int, [_int, _i64, _i64, _i64, _vp, _i64, _vp, _i64]),

@@ -638,11 +638,17 @@ _CODE_T = {torch.float32: _ffi.F32, torch.float64: _ffi.F64, torch.int32: _ffi.I
 
 
 def convert(t, dtype):
-    """astype on the device between float32/float64/int32/int64/bool."""
+    """astype on the device between float32/float64/int32/int64/bool, and from any of those or a complex type to
+    complex64/complex128 (`spamd_cplx_convert`; complex -> real discards a part and is not a device conversion)."""
     dtype = torch_dtype(dtype)
     if t.dtype == dtype:
         return t
     dev = require_hip(t)
+    if dtype in _COMPLEX_CODE and (t.dtype in _CODE_T or t.dtype in _COMPLEX_CODE):
+        out = torch.empty(t.shape, dtype=dtype, device=dev)
+        _ffi.call("spamd_cplx_convert", _CODE_T.get(t.dtype, _COMPLEX_CODE.get(t.dtype)), _COMPLEX_CODE[dtype], t.numel(),
+                  ptr(t.contiguous()), ptr(out), stream_ptr(dev))
+        return out
     if t.dtype not in _CODE_T or dtype not in _CODE_T:
         raise TypeError(f"hip backend cannot convert {t.dtype} -> {dtype}")
     out = torch.empty(t.shape, dtype=dtype, device=dev)

@@ -186,6 +186,158 @@ def _reduce_on_host(x, method, axis, keepdims, kwargs, out_gcxs):
     return out.asformat("gcxs") if out_gcxs else out
 
 
+_COMPLEX = (torch.complex64, torch.complex128)
+COMPLEX_LONG_RUN = 1 << 12      # runs from this length on are summed by `spamd_cplx_sum_long` (leaves spread over threads) ...
+COMPLEX_LONG_MAX_RUNS = 64      # ... when the reduction has at most this many runs (one launch sequence per long run)
+
+
+def pairwise_order_sum(x):
+    """`np.add.reduceat(x, [0])[0]` for a 1-D complex array, restated: x0 + P(x1 .. x(m-1)) per component with NumPy's
+    pairwise sum P over complex values - the order the device sums reproduce (csrc/ewise_complex.hip).  Pure NumPy
+    scalars, slow: the contract's written form, used by the tests."""
+    x = np.asarray(x)
+    real = x.real.dtype.type
+
+    def P(v):
+        c = len(v)
+        if c < 4:
+            re, im = real(-0.0), real(-0.0)
+            for e in v:
+                re, im = re + e.real, im + e.imag
+            return re, im
+        if c <= 64:
+            ar, ai = [v[j].real for j in range(4)], [v[j].imag for j in range(4)]
+            whole = c - c % 4
+            for t in range(4, whole, 4):
+                for j in range(4):
+                    ar[j], ai[j] = ar[j] + v[t + j].real, ai[j] + v[t + j].imag
+            re, im = (ar[0] + ar[1]) + (ar[2] + ar[3]), (ai[0] + ai[1]) + (ai[2] + ai[3])
+            for e in v[whole:]:
+                re, im = re + e.real, im + e.imag
+            return re, im
+        c1 = (c - c % 8) // 2
+        (lr, li), (rr, ri) = P(v[:c1]), P(v[c1:])
+        return lr + rr, li + ri
+
+    if len(x) == 1:
+        return x[0]
+    with np.errstate(all="ignore"):
+        re, im = P(x[1:])
+        out = np.empty(1, dtype=x.dtype)
+        out.real[0], out.imag[0] = x[0].real + re, x[0].imag + im
+    return out[0]
+
+
+def _complex_reducible(x, name, dtype, kwargs):
+    """Complex sums and products with a device form that is `ufunc.reduceat`'s own order (decided on the host, before
+    anything is launched): add with any fill value, multiply with a fill value of exactly 0 or 1 (the fold-in of any other
+    fill value is `np.power(fill, n_missing)`, which has no exact device form)."""
+    if name not in ("add", "multiply") or kwargs or x.data.dtype not in _COMPLEX:
+        return False
+    if dtype is not None and np.dtype(dtype) != np.dtype(x.dtype):
+        return False
+    if name == "multiply":
+        fv = np.asarray(x.fill_value).astype(x.dtype)
+        return fv.tobytes() in (np.zeros((), x.dtype).tobytes(), np.ones((), x.dtype).tobytes())
+    return True
+
+
+def complex_segment_reduce(data, starts, count, op):
+    """The runs data[starts[g] : starts[g + 1]] reduced in `ufunc.reduceat`'s order (`spamd_cplx_segment_reduce`, long runs
+    of a reduction with few runs by `spamd_cplx_sum_long`).  `starts`: device int64[count + 1]."""
+    dev = require_hip(data, starts)
+    n = int(data.numel())
+    code = K.product_code(data.dtype)
+    data = data.contiguous()
+    out = torch.empty(count, dtype=data.dtype, device=dev)
+    s = stream_ptr(dev)
+    long_runs = []
+    if op == "add" and count <= COMPLEX_LONG_MAX_RUNS and n >= COMPLEX_LONG_RUN:
+        hs = K.read_words(starts)
+        long_runs = [(g, int(hs[g]), int(hs[g + 1] - hs[g])) for g in range(count) if hs[g + 1] - hs[g] >= COMPLEX_LONG_RUN]
+    _ffi.call("spamd_cplx_segment_reduce", 0 if op == "add" else 1, code, n, ptr(data), ptr(starts), count,
+              COMPLEX_LONG_RUN - 1 if long_runs else 0, ptr(out), s)
+    esz = data.element_size()
+    for g, start, m in long_runs:
+        wsb = int(_ffi.lib().spamd_cplx_sum_long_ws_bytes(m))
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        _ffi.call("spamd_cplx_sum_long", code, m, data.data_ptr() + start * esz, out.data_ptr() + g * esz, ptr(ws), wsb, s)
+    return out
+
+
+def _reduce_complex(x, name, axis, keepdims, out_gcxs):
+    """`_reduce_on_host`'s algorithm for complex sums and products with every step on the device: kept axes first by a key
+    permutation and one stable sort, runs of equal group id, each run reduced in `ufunc.reduceat`'s own order, the implicit
+    fill entries folded in as `SparseArray.reduce` does (reference _sparse_array.py:398-423): `red + fill * n_missing`
+    with the product formed in complex128 by NumPy's array multiply and the sum cast back; `red * 1` / `red * 0`-or-1 for
+    a product.  No stored value crosses to the host."""
+    from ._coo import COO
+    from ._umath import _full, binary_arrays, select
+
+    kept = tuple(ax for ax in range(x.ndim) if ax not in set(axis))
+    n_groups = prod(x.shape[d] for d in kept)
+    n_cols = prod(x.shape[d] for d in axis)
+    dev = x.device
+    data = x.data
+    n = int(data.numel())
+    fv = np.asarray(x.fill_value).astype(x.dtype)[()]
+    with np.errstate(all="ignore"):
+        result_fill = np.asarray(_SUPER[name](fv, n_cols)).astype(x.dtype)[()]
+    if n:
+        if kept:
+            keys = x.linear_loc()
+            order = kept + tuple(axis)
+            if order != tuple(range(x.ndim)):
+                keys, perm = K.sort_keys(K.permute_keys(keys, x.shape, order), max(x.size - 1, 1))
+                data = K.gather(data, perm)
+            gk = binary_arrays("floor_divide_i64", keys, _scalar_dev(max(n_cols, 1), torch.int64, dev), b_scalar=True)
+            heads = K.flag_heads(gk)
+            offs = K.exclusive_scan(heads)
+            count = int(offs[-1])
+            gids = K.compact(gk, heads, offs, count)
+            iota = torch.empty(n, dtype=torch.int64, device=dev)
+            _ffi.call("spamd_iota", n, ptr(iota), stream_ptr(dev))
+            starts = torch.cat([K.compact(iota, heads, offs, count), _scalar_dev(n, torch.int64, dev)])
+        else:       # one group: the keys say nothing
+            count = 1
+            gids = torch.zeros(1, dtype=torch.int64, device=dev)
+            starts = torch.tensor([0, n], dtype=torch.int64, device=dev)
+        red = complex_segment_reduce(data, starts, count, name)
+        # ---- the implicit entries (n_missing per group), in complex128 as NumPy forms `fill * int64 array`
+        n_fill = binary_arrays("subtract", _scalar_dev(n_cols, torch.int64, dev),
+                               binary_arrays("subtract", starts[1:].contiguous(), starts[:-1].contiguous()), a_scalar=True)
+        full = binary_arrays("equal", n_fill, _scalar_dev(0, torch.int64, dev), b_scalar=True, out_bool_as=torch.uint8)
+        wide = torch.complex128
+        if name == "add":
+            contrib = binary_arrays("multiply", _scalar_dev(complex(fv), wide, dev), K.convert(n_fill, wide), a_scalar=True)
+            contrib = select(full, _full(count, 0, wide, dev), contrib)     # (a full group adds the identity, not fill * 0)
+        else:
+            with np.errstate(all="ignore"):
+                some = np.power(fv, np.array([1, max(n_cols, 1)], dtype=np.int64))      # fill is 0 or 1: one value for every count
+            if some[0].tobytes() != some[1].tobytes():
+                raise _ffi.HipBackendError(f"np.power({fv!r}, n) is not constant")
+            contrib = select(full, _full(count, 1, wide, dev), _full(count, some[0], wide, dev))
+        vals = K.convert(binary_arrays(name, K.convert(red, wide), contrib), data.dtype)
+        flags = K.flag_ne_bits(vals, result_fill)
+        foffs = K.exclusive_scan(flags)
+        cnt = int(foffs[-1])
+        if cnt != count:
+            gids, vals = K.compact(gids, flags, foffs, cnt), K.compact(vals, flags, foffs, cnt)
+    else:
+        vals = data[:0]
+        gids = torch.empty(0, dtype=torch.int64, device=dev)
+    out = COO._from_sorted_keys(gids, vals, (n_groups,), result_fill, x._index_dtype)
+    out = out.reshape(tuple(x.shape[d] for d in kept))
+    if keepdims:
+        shape = list(x.shape)
+        for ax in axis:
+            shape[ax] = 1
+        out = out.reshape(shape)
+    if out.ndim == 0:
+        return COO.from_numpy(out.todense_device())
+    return out.asformat("gcxs") if out_gcxs else out
+
+
 _SCALAR_PLANS = {}      # (ufunc, value dtype, fill value, dtype keyword) -> the reduction's scalar results (see reduce_impl)
 
 
@@ -244,12 +396,14 @@ def reduce_impl(x, method, axis=(0,), keepdims=False, _no_merge=False, **kwargs)
         raise ValueError(f"Performing this reduction operation would produce a dense result: {method!s}")
     dtype = kwargs.pop("dtype", None)
     if not _device_reducible(x, name, dtype, kwargs):
-        if dtype is not None:
-            kwargs["dtype"] = dtype
         if not isinstance(axis, tuple):
             axis = (axis,)
         if axis == (None,):
             axis = tuple(range(x.ndim))
+        if isinstance(method, np.ufunc) and _complex_reducible(x, name, dtype, kwargs):
+            return _reduce_complex(x, name, axis, keepdims, out_gcxs)
+        if dtype is not None:
+            kwargs["dtype"] = dtype
         return _reduce_on_host(x, method, axis, keepdims, kwargs, out_gcxs)
     if not isinstance(axis, tuple):
         axis = (axis,)

@@ -28,7 +28,15 @@ _TO_BOOL = {"greater", "greater_equal", "less", "less_equal", "equal", "not_equa
 _BITWISE = {"bitwise_and", "bitwise_or", "bitwise_xor", "left_shift", "right_shift"}
 _UNARY = {"negative": "negative", "absolute": "absolute", "fabs": "absolute", "positive": "positive",
           "logical_not": "logical_not", "square": None}
-_DTYPES = {np.dtype("float32"), np.dtype("float64"), np.dtype("int32"), np.dtype("int64"), np.dtype("uint8"), np.dtype("bool")}
+_DTYPES = {np.dtype("float32"), np.dtype("float64"), np.dtype("int32"), np.dtype("int64"), np.dtype("uint8"), np.dtype("bool"),
+           np.dtype("complex64"), np.dtype("complex128")}
+# complex values: only the functions whose device form is NumPy's loop bit for bit (`_umath._CBIN`, negative, positive,
+# conjugate, square as the fused x * x); `abs` of a complex value is within 4 ulp, not identical - like the transcendental
+# functions it is not traced; `x ** 2` is NOT x * x for complex values (NumPy's complex power multiplies unfused)
+_COMPLEX_BIN = {"add", "subtract", "multiply", "divide", "true_divide", "equal", "not_equal"}
+_COMPLEX_UN = {"negative", "positive", "conjugate", "square"}
+_COMPLEX_GRAPH = [False]      # set while a callable with a complex ARRAY operand is traced (a complex scalar next to real arrays
+#                               alone keeps the host path, as before)
 
 
 class Untraceable(Exception):
@@ -40,7 +48,7 @@ class _Node:
 
     def __init__(self, op, args, dummy):
         dummy = np.asarray(dummy)
-        if dummy.dtype not in _DTYPES:
+        if dummy.dtype not in _DTYPES or (dummy.dtype.kind == "c" and not _COMPLEX_GRAPH[0]):
             raise Untraceable(f"dtype {dummy.dtype}")
         self.op, self.args, self.dummy = op, args, dummy.reshape(-1)[:1].copy() if dummy.size else dummy
 
@@ -50,7 +58,7 @@ def _dummy_of(v):
 
 
 def _is_scalar(v):
-    return isinstance(v, (bool, int, float, np.generic)) or (isinstance(v, np.ndarray) and v.ndim == 0)
+    return isinstance(v, (bool, int, float, complex, np.generic)) or (isinstance(v, np.ndarray) and v.ndim == 0)
 
 
 class Sym(NDArrayOperatorsMixin):
@@ -72,6 +80,14 @@ class Sym(NDArrayOperatorsMixin):
                 raise Untraceable(f"operand of type {type(v).__name__}")
         with np.errstate(all="ignore"):
             dummy = ufunc(*[_dummy_of(v) for v in inputs])
+        if any(np.asarray(_dummy_of(v)).dtype.kind == "c" for v in inputs):
+            if len(inputs) == 2 and name in _COMPLEX_BIN:
+                return Sym(_Node("divide" if name == "true_divide" else name, tuple(inputs), dummy))
+            if len(inputs) == 1 and name in _COMPLEX_UN:
+                if name == "square":
+                    return Sym(_Node("multiply", (inputs[0], inputs[0]), dummy))
+                return Sym(_Node(name, tuple(inputs), dummy))
+            raise Untraceable(f"{name} of complex values")
         if name == "power" and len(inputs) == 2 and _is_scalar(inputs[1]) and not isinstance(inputs[1], (bool, np.bool_)) \
                 and inputs[1] == 2 and isinstance(inputs[0], Sym):
             return Sym(_Node("multiply", (inputs[0], inputs[0]), dummy))      # x ** 2 is x * x, exactly
@@ -115,22 +131,25 @@ class Sym(NDArrayOperatorsMixin):
 
 def build(func, args_spec):
     """args_spec: per positional argument either ("array", np dtype) or ("scalar", value).  -> root Sym, or None."""
-    syms = []
-    for i, (kind, x) in enumerate(args_spec):
-        if kind == "array":
-            if np.dtype(x) not in _DTYPES:
-                return None
-            syms.append(Sym(_Node("leaf", (i,), np.zeros(1, dtype=x))))
-        else:
-            if not _is_scalar(x):
-                return None
-            syms.append(x)
+    _COMPLEX_GRAPH[0] = any(kind == "array" and np.dtype(x).kind == "c" for kind, x in args_spec)
     try:
+        syms = []
+        for i, (kind, x) in enumerate(args_spec):
+            if kind == "array":
+                if np.dtype(x) not in _DTYPES:
+                    return None
+                syms.append(Sym(_Node("leaf", (i,), np.zeros(1, dtype=x))))
+            else:
+                if not _is_scalar(x):
+                    return None
+                syms.append(x)
         root = func(*syms)
     except Untraceable:
         return None
     except Exception:   # noqa: BLE001 - whatever else goes wrong with symbolic operands: the host path decides
         return None
+    finally:
+        _COMPLEX_GRAPH[0] = False
     return root if isinstance(root, Sym) else None
 
 
@@ -184,6 +203,8 @@ def run(root, arrays, n, devi):
             r = torch.empty(n, dtype=torch_dtype(out_dt), device=devi)
             _ffi.call("spamd_ewise_select", r.element_size(), n, ptr(mask.contiguous().view(torch.uint8)), ptr(ta.contiguous()),
                       int(sa), ptr(tb.contiguous()), int(sb), ptr(r), stream_ptr(devi))
+        elif op == "conjugate":      # (complex operands only: see __array_ufunc__)
+            r = unary_array(op, value(node.args[0], out_dt)[0])
         elif op in ("negative", "absolute", "positive", "logical_not"):
             (a,) = node.args
             src_dt = _dummy_of(a).dtype if op == "logical_not" else out_dt
@@ -204,6 +225,8 @@ def run(root, arrays, n, devi):
                 comp = out_dt
             if comp not in _DTYPES:
                 raise Untraceable(f"compute dtype {comp}")
+            if comp.kind == "c" and op not in _COMPLEX_BIN:
+                raise Untraceable(f"{op} of complex values")
             ta, sa = value(a, comp)
             tb, sb = value(b, comp)
             if sa and sb:      # two scalars: NumPy already folded them into the dummy
@@ -216,7 +239,8 @@ def run(root, arrays, n, devi):
                     name = "logical_and"
                 elif comp == np.dtype(bool) and op in ("subtract", "divide"):
                     raise Untraceable("boolean subtract / divide")
-                if name not in _BIN or (comp not in _COMP_TYPES.get(_BIN[name], (comp,)) and comp != np.dtype(bool)):
+                if name not in _BIN or (comp not in _COMP_TYPES.get(_BIN[name], (comp,)) and comp != np.dtype(bool)
+                                        and comp.kind != "c"):
                     raise Untraceable(f"no device kernel for {name} in {comp}")
                 r = binary_arrays(name, ta, tb, a_scalar=sa, b_scalar=sb)
                 if r.dtype == torch.uint8 and out_dt == np.dtype(bool):

@@ -46,12 +46,53 @@ _CODE = {torch.float32: _ffi.F32, torch.float64: _ffi.F64, torch.int32: _ffi.I32
          torch.uint8: _ffi.U8, torch.bool: _ffi.U8}
 
 
+# complex64 / complex128 values (csrc/ewise_complex.hip, csrc/merge_complex.hip): the functions with a device form that is
+# NumPy's own loop statement for statement (binary codes = `_BIN`'s; `absolute` is within 4 ulp, everything else exact).  Every
+# other function of complex values - transcendental functions, power, reciprocal, sign, ordered comparisons, maximum /
+# minimum, logical_* - is evaluated by NumPy on the host (`_elemwise_general`).
+_CBIN = {"add": 0, "subtract": 1, "multiply": 2, "divide": 3, "true_divide": 3, "equal": 36, "not_equal": 37}
+_CUN = {"negative": 0, "positive": 22, "conjugate": 96, "conj": 96, "square": 20, "absolute": 1, "abs": 1, "real": 97,
+        "imag": 98, "isnan": 64, "isinf": 65, "isfinite": 66}
+_CUN_REAL = {1, 97, 98}
+_CCODE = {torch.complex64: _ffi.C64, torch.complex128: _ffi.C128}
+_CREAL = {torch.complex64: torch.float32, torch.complex128: torch.float64}
+
+
 def _as_u8(t):
     return t.view(torch.uint8) if t.dtype == torch.bool else t
 
 
+def _cbinary_arrays(name, a, b, a_scalar, b_scalar, out_bool_as):
+    if name not in _CBIN:
+        raise TypeError(f"{name} of complex values has no device kernel")
+    code = _CBIN[name]
+    devi = require_hip(a, b)
+    a, b = a.contiguous(), b.contiguous()
+    if a.dtype != b.dtype:
+        raise TypeError(f"binary_arrays needs one compute dtype, got {a.dtype} and {b.dtype}")
+    n = int(b.numel() if a_scalar else a.numel())
+    out = torch.empty(n, dtype=torch.uint8 if code in _TO_BOOL_BIN else a.dtype, device=devi)
+    _ffi.call("spamd_cplx_binary", code, _CCODE[a.dtype], n, ptr(a), int(a_scalar), ptr(b), int(b_scalar), ptr(out),
+              stream_ptr(devi))
+    return out.view(torch.bool) if code in _TO_BOOL_BIN and out_bool_as == torch.bool else out
+
+
+def _cunary_array(name, a):
+    if name not in _CUN:
+        raise TypeError(f"{name} of complex values has no device kernel")
+    code = _CUN[name]
+    devi = require_hip(a)
+    a = a.contiguous()
+    out_t = torch.uint8 if code in (64, 65, 66) else (_CREAL[a.dtype] if code in _CUN_REAL else a.dtype)
+    out = torch.empty(a.numel(), dtype=out_t, device=devi)
+    _ffi.call("spamd_cplx_unary", code, _CCODE[a.dtype], a.numel(), ptr(a), ptr(out), stream_ptr(devi))
+    return out.view(torch.bool) if out_t == torch.uint8 else out
+
+
 def binary_arrays(name, a, b, a_scalar=False, b_scalar=False, out_bool_as=torch.bool):
     """out = a (op) b on equal-length device arrays (or a 1-element array broadcast as scalar)."""
+    if a.dtype in _CCODE or b.dtype in _CCODE:
+        return _cbinary_arrays(name, a, b, a_scalar, b_scalar, out_bool_as)
     if name == "floor_divide_i64":  # non-negative int64 keys: truncation == floor
         code, name = 3, "divide"
     else:
@@ -77,6 +118,8 @@ def binary_arrays(name, a, b, a_scalar=False, b_scalar=False, out_bool_as=torch.
 
 
 def unary_array(name, a):
+    if a.dtype in _CCODE:
+        return _cunary_array(name, a)
     code = _UN[name]
     devi = require_hip(a)
     was_bool = a.dtype == torch.bool
@@ -91,7 +134,7 @@ def select(mask, a, b):
     out = b; out[mask] = a[mask]."""
     devi = require_hip(mask, a, b)
     m = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
-    if m.dtype == torch.uint8 and a.dtype == b.dtype and a.element_size() in (1, 4, 8) and a.numel() == b.numel() == m.numel():
+    if m.dtype == torch.uint8 and a.dtype == b.dtype and a.element_size() in (1, 4, 8, 16) and a.numel() == b.numel() == m.numel():
         # one pass (`spamd_ewise_select`: 0/1 mask bytes, values moved bit-wise) instead of clone + flags + scan + iota +
         # compact + gather + scatter with a host read in the middle (late round 6: where(x > 0.5, x, 0) at 10^7 stored
         # elements 1.51 ms, half of it here)
@@ -114,6 +157,10 @@ def select(mask, a, b):
 
 def _full(n, value, dtype, devi):
     t = torch.empty(n, dtype=dtype, device=devi)
+    if n and dtype in _CCODE:
+        v = np.asarray(value).astype(dev.np_dtype(dtype))[()]
+        _ffi.call("spamd_cplx_fill", _CCODE[dtype], n, ptr(t), float(v.real), float(v.imag), stream_ptr(devi))
+        return t
     if n:
         npdt = dev.np_dtype(dtype) if dtype != torch.bool else np.dtype("uint8")
         bits = int(np.asarray(value, dtype=npdt).reshape(1).view(f"u{npdt.itemsize}")[0])
@@ -223,6 +270,8 @@ def merge_union(name, ka, va, kb, vb, fill_a, fill_b, fill_out):
     """Fused merge-path union: (keys, values) of func(a or fill_a, b or fill_b) over the union of
     two canonical key arrays, results bit-equal to `fill_out` dropped (csrc/merge.hip).
     `va`/`vb` share the compute dtype; `fill_out` is a NumPy scalar of the output dtype."""
+    if va.dtype in _CCODE:
+        return _cmerge_union(name, ka, va, kb, vb, fill_a, fill_b, fill_out)
     code = _BIN[name]
     devi = require_hip(ka, kb, va, vb)
     bool_out = code in _TO_BOOL_BIN or (va.dtype == torch.bool and vb.dtype == torch.bool)
@@ -277,6 +326,44 @@ def merge_union(name, ka, va, kb, vb, fill_a, fill_b, fill_out):
     vals = torch.empty(total, dtype=out_t, device=devi)
     _ffi.call("spamd_merge_union", 1, *args, 0, ptr(offs), ptr(keys), ptr(vals), s)
     return keys, (vals.view(torch.bool) if bool_out else vals)
+
+
+def _cmerge_union(name, ka, va, kb, vb, fill_a, fill_b, fill_out):
+    """`merge_union` for complex values (csrc/merge_complex.hip): partition + one pass with look-back; the fill values go
+    by address (a complex128 value is 16 bytes).  `fill_out`: a complex scalar, or a uint8 0 / 1 for equal / not_equal."""
+    import ctypes
+
+    code = _CBIN[name]
+    devi = require_hip(ka, kb, va, vb)
+    to_bool = code in _TO_BOOL_BIN
+    va, vb = va.contiguous(), vb.contiguous()
+    if va.dtype != vb.dtype:
+        raise TypeError(f"merge_union needs one compute dtype, got {va.dtype} and {vb.dtype}")
+    comp_np = dev.np_dtype(va.dtype)
+    na, nb = int(ka.numel()), int(kb.numel())
+    out_t = torch.uint8 if to_bool else va.dtype
+    nblocks = int(_ffi.lib().spamd_merge_num_blocks(na, nb))
+    if nblocks == 0:
+        e = torch.empty(0, dtype=out_t, device=devi)
+        return torch.empty(0, dtype=torch.int64, device=devi), (e.view(torch.bool) if to_bool else e)
+    s = stream_ptr(devi)
+    fa = np.asarray(fill_a).astype(comp_np).reshape(1)
+    fb = np.asarray(fill_b).astype(comp_np).reshape(1)
+    fo = np.asarray(fill_out).astype(np.uint8 if to_bool else comp_np).reshape(1)
+    part = torch.empty(nblocks + 1, dtype=torch.int64, device=devi)
+    _ffi.call("spamd_merge_partition", na, ptr(ka), nb, ptr(kb), ptr(part), s)
+    counts = torch.empty(nblocks + 2, dtype=torch.int64, device=devi)
+    keys = torch.empty(na + nb, dtype=torch.int64, device=devi)
+    vals = torch.empty(na + nb, dtype=out_t, device=devi)
+    _ffi.call("spamd_merge_union_complex", code, _CCODE[va.dtype], na, ptr(ka), ptr(va), nb, ptr(kb), ptr(vb),
+              fa.ctypes.data_as(ctypes.c_void_p), fb.ctypes.data_as(ctypes.c_void_p), fo.ctypes.data_as(ctypes.c_void_p),
+              ptr(part), ptr(counts), ptr(keys), ptr(vals), s)
+    total = int(counts[nblocks + 1])
+    if total * 2 < na + nb:   # a sparse result should not pin the worst-case buffers
+        keys, vals = keys[:total].clone(), vals[:total].clone()
+    else:
+        keys, vals = keys[:total], vals[:total]
+    return keys, (vals.view(torch.bool) if to_bool else vals)
 
 
 def _where(proc, finish):
@@ -544,7 +631,8 @@ def _broadcast_matched(name, func, a, b, shape, out_np, comp_np, finish):
     x, y = (a, b) if x_is_a else (b, a)
     devi = x.device
     comp_t = torch_dtype(comp_np)
-    if comp_np not in (np.dtype("f4"), np.dtype("f8"), np.dtype("i4"), np.dtype("i8")) or np.dtype(out_np) != np.dtype(comp_np):
+    if comp_np not in (np.dtype("f4"), np.dtype("f8"), np.dtype("i4"), np.dtype("i8"), np.dtype("c8"), np.dtype("c16")) \
+            or np.dtype(out_np) != np.dtype(comp_np):
         return None
     fx, fy = np.asarray(x.fill_value).astype(comp_np), np.asarray(y.fill_value).astype(comp_np)
     fill = np.asarray(_np_result(func, *((fx, fy) if x_is_a else (fy, fx)))).astype(out_np)[()]
@@ -593,6 +681,16 @@ def _func_name(func):
     if func is np.ndarray.astype:
         return "astype"
     return getattr(func, "__name__", None)
+
+
+def torch_dtype_of(v):
+    """torch dtype of a dense operand (ndarray / tensor), None when torch has no such type"""
+    if isinstance(v, torch.Tensor):
+        return v.dtype
+    try:
+        return torch_dtype(np.asarray(v).dtype)
+    except (KeyError, TypeError):
+        return None
 
 
 def _scalar_like(x):
@@ -793,7 +891,12 @@ def elemwise(func, *args, **kwargs):
         if func is np.imag and not kwargs and dtype_kw is None and x.data.dtype in _CODE:
             # the imaginary part of a real array: no stored elements, fill 0 of the array's type
             return finish(x.linear_loc()[:0], x.data[:0], shape, _np_result(func, np.asarray(x.fill_value))[()], devi)
-        if name not in _UN or kwargs or x.data.dtype not in _CODE:   # (complex / narrow value types: host-evaluated func)
+        if x.data.dtype in _CCODE and name in _CUN and not kwargs and dtype_kw is None \
+                and (isinstance(func, np.ufunc) or func is np.real or func is np.imag):
+            # complex values: NumPy's loop on the device (abs = hypot: within 4 ulp; everything else bit for bit)
+            fill = _np_result(func, np.asarray(x.fill_value).astype(x.dtype))[()]
+            return finish(x.linear_loc(), unary_array(name, x.data), shape, np.asarray(fill)[()], devi)
+        if name not in _UN or kwargs or x.data.dtype not in _CODE:   # (narrow value types, other complex functions: host-evaluated func)
             return _elemwise_general(func, proc, kwargs, dtype_kw, finish)
         fill = _np_result(func, np.asarray(x.fill_value))[()]
         code, in_np = _UN[name], np.dtype(x.dtype)
@@ -864,7 +967,15 @@ def elemwise(func, *args, **kwargs):
         # NumPy's boolean arithmetic is logical (True + True is True): never a raw uint8 add on the 0/1 bytes
         name = _BOOL_ARITH[name]
         code = _BIN[name]
-    if comp_np not in (np.dtype("f4"), np.dtype("f8"), np.dtype("i4"), np.dtype("i8"), np.dtype("bool"), np.dtype("u1")) \
+    if comp_np.kind == "c":
+        # complex compute type (either operand complex, or a complex scalar next to a real array): the functions of `_CBIN`
+        # on operands the device can convert; decided here, before anything is launched
+        if name not in _CBIN or dtype_kw is not None or comp_np not in (np.dtype("c8"), np.dtype("c16")) \
+                or any(isinstance(v, COO) and v.data.dtype not in _CODE and v.data.dtype not in _CCODE for v in (a, b)) \
+                or any(isinstance(v, (np.ndarray, torch.Tensor)) and torch_dtype_of(v) not in _CODE
+                       and torch_dtype_of(v) not in _CCODE for v in (a, b)):
+            return _elemwise_general(func, proc, kwargs, dtype_kw, finish)
+    elif comp_np not in (np.dtype("f4"), np.dtype("f8"), np.dtype("i4"), np.dtype("i8"), np.dtype("bool"), np.dtype("u1")) \
             or comp_np not in _COMP_TYPES.get(code, (comp_np,)) or (code in _COMP_TYPES and code < 32 and out_np != comp_np):
         return _elemwise_general(func, proc, kwargs, dtype_kw, finish)
     comp_t = torch_dtype(comp_np)
@@ -928,7 +1039,7 @@ def elemwise(func, *args, **kwargs):
             fill_t = allfill[:1].contiguous()
             differs = binary_arrays("not_equal", _as_u8(allfill) if out_np == np.dtype(bool) else allfill, 
                                     _as_u8(fill_t) if out_np == np.dtype(bool) else fill_t, b_scalar=True, out_bool_as=torch.uint8)
-            if out_np.kind == "f" and np.isnan(fill):   # NaN == NaN for this purpose
+            if out_np.kind in "fc" and np.isnan(fill):   # NaN == NaN for this purpose
                 differs = unary_array("logical_not", unary_array("isnan", allfill)).view(torch.uint8)
             nonconst = int(differs.numel()) - K.count_eq_bits(differs, 0)
         else:

@@ -496,6 +496,9 @@ extern "C" int spamd_ewise_binary(int op, int val_dtype, int64_t n, const void* 
 
 // out[i] = mask[i] ? a[i] : b[i]  (np.where on aligned arrays; a / b may be one-element arrays broadcast as scalars);
 // values are moved bit-wise
+struct alignas(8) Word128 {
+  uint64_t lo, hi;
+};
 template <typename U>
 __global__ void __launch_bounds__(256) select_kernel(const uint8_t* __restrict__ mask, const U* __restrict__ a, int as,
                                                      const U* __restrict__ b, int bs, int64_t n, U* __restrict__ out) {
@@ -512,6 +515,7 @@ extern "C" int spamd_ewise_select(int elem_bytes, int64_t n, const void* mask_u8
     case 1: hipLaunchKernelGGL(select_kernel<uint8_t>, dim3(grid_for(n)), dim3(256), 0, s, (const uint8_t*)mask_u8, (const uint8_t*)a, as, (const uint8_t*)b, bs, n, (uint8_t*)out); break;
     case 4: hipLaunchKernelGGL(select_kernel<uint32_t>, dim3(grid_for(n)), dim3(256), 0, s, (const uint8_t*)mask_u8, (const uint32_t*)a, as, (const uint32_t*)b, bs, n, (uint32_t*)out); break;
     case 8: hipLaunchKernelGGL(select_kernel<uint64_t>, dim3(grid_for(n)), dim3(256), 0, s, (const uint8_t*)mask_u8, (const uint64_t*)a, as, (const uint64_t*)b, bs, n, (uint64_t*)out); break;
+    case 16: hipLaunchKernelGGL(select_kernel<Word128>, dim3(grid_for(n)), dim3(256), 0, s, (const uint8_t*)mask_u8, (const Word128*)a, as, (const Word128*)b, bs, n, (Word128*)out); break;   // complex128 (8-byte aligned)
     default: return SPAMD_ETYPE;
   }
   return launch_status();
