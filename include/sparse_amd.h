@@ -37,6 +37,8 @@ extern "C" {
                       * spamd_segment_reduce with op = add) and the complex elementwise / reduction entry points (spamd_cplx_*,
                       * spamd_merge_union_complex) */
 #define SPAMD_C128 7 /* complex128: interleaved (re, im) float64 pairs - the same entry points */
+#define SPAMD_F16 8  /* IEEE float16: dense operands of the SDDMM entry points only (spamd_sddmm, spamd_sddmm_panels,
+                      * spamd_sddmm_mfma_tiles_typed) */
 
 #define SPAMD_MAX_NDIM 16 /* largest array rank the key kernels accept */
 
@@ -589,7 +591,7 @@ int spamd_dense_nonfill(int val_bytes, int64_t n, const void* vals, uint64_t fil
  *   replaces the reference's formulation `s * (a @ b)` (examples/sddmm_example.py:51-52: a dense
  *   BLAS GEMM of the full M x N product + `_Elemwise` gather, _umath.py:602-633).
  *   A is M x K row-major (lda), Bt = B^T is N x K row-major (ldb): both K-contiguous, 16-byte
- *   aligned rows.  in_dtype BF16|F32 -> fp32 accumulate and F32 mask/out; F64 -> F64.
+ *   aligned rows.  in_dtype BF16|F16|F32 -> fp32 accumulate and F32 mask/out; F64 -> F64.
  * ------------------------------------------------------------------------------------- */
 int spamd_sddmm(int in_dtype, int s_dtype, int idx_dtype, int64_t nnz, const void* rows, const void* cols,
                 const void* s_data, const void* A, int64_t lda, const void* Bt, int64_t ldb, int64_t K, void* out,
@@ -609,7 +611,7 @@ int spamd_sddmm(int in_dtype, int s_dtype, int idx_dtype, int64_t nnz, const voi
 int spamd_sddmm_has_panels(int in_dtype, int64_t K); /* 1: spamd_sddmm_panels has a kernel for this K */
 int spamd_sddmm_panel_keys(int idx_dtype, int64_t nnz, const void* cols, int64_t width, int64_t per_xcd, void* keys,
                            void* stream);
-/* Rows of exactly 1 KB (fp32 K = 256, fp64 K = 128, bf16 K = 512): with `part` (nnz words of the accumulator type - fp32, or
+/* Rows of exactly 1 KB (fp32 K = 256, fp64 K = 128, bf16 / f16 K = 512): with `part` (nnz words of the accumulator type - fp32, or
  * fp64 for F64 operands - of caller-owned scratch) the product runs as TWO passes over 512-byte half-rows (the first leaves its
  * sums in `part` in panel order, the second adds its half and writes s * sum), so that a panel holds twice the Bt rows in the
  * same L2 bytes and A is streamed half as often (config 4 fp32: 6.4 GB -> ~2.5 GB of fabric traffic); the panels are then
@@ -626,7 +628,7 @@ int spamd_sddmm_panels(int in_dtype, int s_dtype, int idx_dtype, int64_t nnz, co
  * Same reference formulation (examples/sddmm_example.py:51-52).  Plan: spamd_sddmm_tile_keys -> stable sort of the keys
  * with the sample index as payload (spamd_sort_pairs) -> spamd_flag_heads / spamd_exclusive_scan / spamd_compact give
  * seg_start[nseg + 1] -> spamd_sddmm_tile_classify -> scan + compact give the list of dense tiles and of left-over
- * samples.  bf16 operands only, K a multiple of 16, 16-byte aligned rows. */
+ * samples.  bf16 operands (float16: spamd_sddmm_mfma_tiles_typed), K a multiple of 16, 16-byte aligned rows. */
 int spamd_sddmm_tile_size(void);
 int spamd_sddmm_tile_keys(int idx_dtype, int64_t nnz, const void* rows, const void* cols, int64_t tile_cols,
                           int64_t* keys, void* stream);
@@ -636,6 +638,24 @@ int spamd_sddmm_mfma_tiles(int idx_dtype, int64_t ntiles, const int64_t* tiles, 
                            const int64_t* keys_sorted, const int64_t* perm, int64_t tile_cols, int64_t M, int64_t N,
                            const void* rows, const void* cols, const float* s_data, const void* A, int64_t lda,
                            const void* Bt, int64_t ldb, int64_t K, float* out, void* stream);
+/* The same with the operands' element type as an argument: in_dtype BF16 (= spamd_sddmm_mfma_tiles) | F16
+ * (v_mfma_f32_32x32x16_f16: the same lane maps, tile plan and cycles).  Any other in_dtype: SPAMD_EINVAL. */
+int spamd_sddmm_mfma_tiles_typed(int in_dtype, int idx_dtype, int64_t ntiles, const int64_t* tiles, const int64_t* seg_start,
+                                 const int64_t* keys_sorted, const int64_t* perm, int64_t tile_cols, int64_t M, int64_t N,
+                                 const void* rows, const void* cols, const float* s_data, const void* A, int64_t lda,
+                                 const void* Bt, int64_t ldb, int64_t K, float* out, void* stream);
+
+/* A9 with an N-D mask [l_1 .. l_p, M, N] over operands A [(leading), M, K] and Bt [(leading), N, K] whose leading axes
+ * broadcast against the mask's (the same sampled product; the reference's `s * (a @ b)`, examples/sddmm_example.py:51-52,
+ * broadcasts the dense product the same way): the fold of every stored element to the 2-D pair
+ *   rows[n] = (sum_d coords[d][n] * a_strides[d]) * M + coords[p][n],   cols[n] = (sum_d coords[d][n] * b_strides[d]) * N + coords[p + 1][n]
+ * with which spamd_sddmm / spamd_sddmm_panels / spamd_sddmm_mfma_tiles run on A as [Ba * M, K] and Bt as [Bb * N, K].
+ * coords: [nlead + 2, nnz] of idx_dtype (I32 | I64), row pitch ldc elements; a_strides / b_strides: nlead HOST words, the
+ * stride of each leading axis in the operand's batch ordinal (0 where the operand is broadcast); rows / cols: nnz words of
+ * out_dtype I32 (the caller knows Ba * M and Bb * N fit) | I64.  One pass over the coordinates. */
+int spamd_sddmm_batch_fold(int idx_dtype, int out_dtype, int nlead, int64_t nnz, const void* coords, int64_t ldc,
+                           const int64_t* a_strides, const int64_t* b_strides, int64_t M, int64_t N, void* rows, void* cols,
+                           void* stream);
 
 /* =======================================================================================
  * A11  Complex elementwise functions, conversions and reductions (val_dtype C64 | C128; SPAMD_ETYPE otherwise)

@@ -34,16 +34,22 @@ def asarray(obj, /, *, dtype=None, format="coo", copy=False, device=None):
 
 def sddmm(s, a, b=None, *, bt=None):
     """Sampled dense-dense matmul: `s * (a @ b)` evaluated only at the stored positions of the
-    2-D sparse mask `s` (the reference's formulation, examples/sddmm_example.py:51-52, forms the
+    sparse mask `s` (the reference's formulation, examples/sddmm_example.py:51-52, forms the
     whole dense product first).  Pass `b` (K x N) or its transpose `bt` (N x K, K-contiguous:
-    avoids a device transpose).  Dense operands may be bfloat16/float32/float64 torch tensors
-    (bf16/fp32 accumulate in fp32) or float ndarrays.  Result has the format of `s`, zeros pruned."""
+    avoids a device transpose).  Dense operands may be bfloat16/float16/float32/float64 torch tensors
+    or float16/float32/float64 ndarrays, both of one type (16-bit and fp32 operands accumulate in
+    fp32 and give float32 values).  Result has the format of `s`, zeros pruned.
+
+    `s` may have more than two dimensions: `a` is (..., M, K), `b` (..., K, N) or `bt` (..., N, K), and
+    their leading axes broadcast against the leading axes of `s.shape` (NumPy's matmul rule, except that
+    the mask's leading shape is the result's: an operand axis is 1 or the mask's size).  The whole stack
+    is one product: the stored elements are folded to 2-D pairs once per mask and leading shapes."""
     from ._dot import _validate_derived
     from ._utils import check_zero_fill_value
 
     check_zero_fill_value(s)
-    if s.ndim != 2:
-        raise ValueError("sddmm needs a 2-D sparse mask")
+    if s.ndim < 2:
+        raise ValueError("sddmm needs a sparse mask of at least 2 dimensions")
     out_gcxs = isinstance(s, GCXS)
     if isinstance(s, COO):
         sc = s
@@ -55,28 +61,42 @@ def sddmm(s, a, b=None, *, bt=None):
     at = dev.to_device(a, sc.device)
     if (b is None) == (bt is None):
         raise ValueError("pass exactly one of b / bt")
-    btt = dev.to_device(bt, sc.device) if bt is not None else dev.to_device(b, sc.device).t().contiguous()
-    if at.shape[0] != s.shape[0] or btt.shape[0] != s.shape[1] or at.shape[1] != btt.shape[1]:
+    btt = dev.to_device(bt, sc.device) if bt is not None else dev.to_device(b, sc.device).transpose(-1, -2).contiguous()
+    M, N = int(s.shape[-2]), int(s.shape[-1])
+    if at.dim() < 2 or btt.dim() < 2 or at.shape[-2] != M or btt.shape[-2] != N or at.shape[-1] != btt.shape[-1]:
         raise ValueError("shape-mismatch for sum")
-    at, btt = K.sddmm_pad_inner(at, btt, sc.nnz)
     _validate_derived(sc)
     # plans depend on the pattern only and are kept on the mask (dropped with its other derived layouts when the
     # coordinates change): the populated 32 x 32 tiles that go to the matrix cores, and - when Bt is larger than an
     # XCD's L2 - the column-panel order of whatever the sampled kernel takes
-    width = K.sddmm_panel_width(btt)
     plans = sc.__dict__.setdefault("_sddmm_plan", {})
+    coords, shape2 = sc.coords, sc.shape
+    if s.ndim > 2 or at.dim() > 2 or btt.dim() > 2:
+        # N-D mask: the stored elements folded to pairs (row', col') over a as [Ba * M, K] and bt as [Bb * N, K]
+        # (csrc/sddmm_batch.hip); the fold and the plans built on it are kept per pair of leading shapes
+        lead, la, lb = tuple(s.shape[:-2]), tuple(at.shape[:-2]), tuple(btt.shape[:-2])
+        sa, nba = K.sddmm_fold_strides(lead, la, "a")
+        sb, nbb = K.sddmm_fold_strides(lead, lb, "b")
+        at, btt = at.reshape(nba * M, at.shape[-1]), btt.reshape(nbb * N, btt.shape[-1])
+        shape2 = (nba * M, nbb * N)
+        plans = plans.setdefault(("fold", la, lb), {})
+        if "coords" not in plans:
+            plans["coords"] = K.sddmm_fold(sc.coords, len(lead), sa, sb, M, N, shape2[0], shape2[1])
+        coords = plans["coords"]
+    at, btt = K.sddmm_pad_inner(at, btt, sc.nnz)
+    width = K.sddmm_panel_width(btt)
 
     def panels_of(subset, tag):
         key = ("panels", tag, width)
         if key not in plans:
-            plans[key] = K.sddmm_panels(sc.coords, sc.shape, width, subset=subset)
+            plans[key] = K.sddmm_panels(coords, shape2, width, subset=subset)
         return plans[key]
 
     vals = None
-    if at.dtype == torch.bfloat16 and btt.dtype == torch.bfloat16 and sc.nnz >= K.SDDMM_TILE_THRESHOLD and at.shape[1] % 16 == 0:
+    if at.dtype in K.SDDMM_HALF_DTYPES and btt.dtype == at.dtype and sc.nnz >= K.SDDMM_TILE_THRESHOLD and at.shape[1] % 16 == 0:
         key = ("tiles", K.SDDMM_TILE_THRESHOLD)
         if key not in plans:
-            plans[key] = K.sddmm_plan(sc.coords, sc.shape)
+            plans[key] = K.sddmm_plan(coords, shape2)
         plan = plans[key]
         if K.sddmm_tiles_pay(plan, at, btt, width):
             # the left-over samples: in panel order if that pays for so many, else as ONE panel (= the mask's own order;
@@ -84,14 +104,14 @@ def sddmm(s, a, b=None, *, bt=None):
             nrest = int(plan.rest.numel())
             rest = None
             if nrest and K.sddmm_has_panels(at.dtype, at.shape[1]):
-                rw = width if K.sddmm_panels_pay(nrest, at, btt, width) else builtins.max(int(sc.shape[1]), 1)
+                rw = width if K.sddmm_panels_pay(nrest, at, btt, width) else builtins.max(int(shape2[1]), 1)
                 key = ("panels", "rest", rw)
                 if key not in plans:
-                    plans[key] = K.sddmm_panels(sc.coords, sc.shape, rw, subset=plan.rest)
+                    plans[key] = K.sddmm_panels(coords, shape2, rw, subset=plan.rest)
                 rest = plans[key]
-            vals = K.sddmm_coo_mfma(plan, sc.coords, sc.shape, sc.data, at, btt, force=True, rest_panels=rest)
+            vals = K.sddmm_coo_mfma(plan, coords, shape2, sc.data, at, btt, force=True, rest_panels=rest)
     if vals is None:
-        vals = K.sddmm_coo(sc.coords, sc.data, at, btt,
+        vals = K.sddmm_coo(coords, sc.data, at, btt,
                            panels=panels_of(None, "all") if K.sddmm_panels_pay(sc.nnz, at, btt, width) else None)
     out = COO(sc.coords, vals, shape=s.shape, has_duplicates=False, sorted=True, prune=True)
     return out.asformat("gcxs", compressed_axes=s.compressed_axes) if out_gcxs else out

@@ -15,6 +15,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sparse_amd.h")
 # dtype codes (include/sparse_amd.h)
 F32, F64, I32, I64, BF16, U8 = 0, 1, 2, 3, 4, 5
 C64, C128 = 6, 7     # the complex products (spamd_spmm_csr_complex, spamd_spgemm_expand, spamd_segment_reduce(add)) and spamd_cplx_*
+F16 = 8              # IEEE float16: dense operands of the SDDMM entry points only
 MAX_NDIM = 16
 EXACT_MULADD = 1
 TILED_GROUP_ENDS = 2
@@ -106,6 +107,9 @@ SIGNATURES = {
     "spamd_sddmm_tile_classify": (_int, [_i64, _vp, _i64, _vp, _vp, _vp]),
     "spamd_sddmm_mfma_tiles": (_int, [_int, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64,
                                       _i64, _vp, _vp]),
+    "spamd_sddmm_mfma_tiles_typed": (_int, [_int, _int, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp,
+                                            _i64, _i64, _vp, _vp]),
+    "spamd_sddmm_batch_fold": (_int, [_int, _int, _int, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "spamd_merge_num_blocks": (_i64, [_i64, _i64]),
     "spamd_merge_partition": (_int, [_i64, _vp, _i64, _vp, _vp, _vp]),
     "spamd_merge_union": (_int, [_int, _int, _int, _i64, _vp, _vp, _i64, _vp, _vp, _C.c_uint64, _C.c_uint64,

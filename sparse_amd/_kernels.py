@@ -1215,9 +1215,27 @@ class SddmmPanels:
         return self._vals
 
 
+SDDMM_HALF_DTYPES = (torch.bfloat16, torch.float16)       # the 16-bit float operand types: fp32 accumulate, matrix-core tiles
+SDDMM_DTYPES = SDDMM_HALF_DTYPES + (torch.float32, torch.float64)
+
+
+def sddmm_code(dt):
+    """C-ABI code of an SDDMM operand type: what `code_of` knows plus float16, which only the SDDMM kernels take.  Kept apart
+    from `code_of` (and from `product_code`), whose TypeError for float16 is the "no device kernel for this dtype" probe of
+    the other layers."""
+    dt = dt if isinstance(dt, torch.dtype) else torch_dtype(dt)
+    if dt not in SDDMM_DTYPES:
+        raise TypeError(f"sddmm supports bfloat16/float16/float32/float64 dense operands, got {dt}")
+    return _ffi.F16 if dt is torch.float16 else code_of(dt)
+
+
 def sddmm_has_panels(dtype, Kd):
     """Does spamd_sddmm_panels have a kernel for rows of `Kd` elements of `dtype`?"""
-    return dtype in (torch.bfloat16, torch.float32, torch.float64) and bool(_ffi.lib().spamd_sddmm_has_panels(code_of(dtype), int(Kd)))
+    try:
+        code = sddmm_code(dtype)
+    except (TypeError, KeyError):
+        return False
+    return bool(_ffi.lib().spamd_sddmm_has_panels(code, int(Kd)))
 
 
 SDDMM_PAD_MIN_NNZ = 200_000     # samples from which padding the inner dimension to a row-cached kernel's row length pays the two copies
@@ -1230,7 +1248,7 @@ def sddmm_pad_inner(a, bt, nnz):
     ran through the generic gather, 0.61 / 0.85 ms at config 4's mask, without a panel order; as 512-byte rows 0.38 / 0.33 ms
     plus two copies of ~0.03 ms).  Zeros add nothing to a dot product: the sums are those of the padded kernels' lane order,
     in the mask's own order and in panel order alike."""
-    if a.dtype not in (torch.bfloat16, torch.float32, torch.float64) or a.dim() != 2 or nnz < SDDMM_PAD_MIN_NNZ:
+    if a.dtype not in SDDMM_DTYPES or a.dim() != 2 or nnz < SDDMM_PAD_MIN_NNZ:
         return a, bt
     esz, k = a.element_size(), int(a.shape[1])
     if k == 0 or sddmm_has_panels(a.dtype, k):
@@ -1252,7 +1270,7 @@ def sddmm_panel_width(bt):
         return 0
     if SDDMM_TWO_PASS:
         # rows of 1 KB run as two passes over 512-byte halves (round 5): a panel is sized for the half-rows
-        row_bytes = int(_ffi.lib().spamd_sddmm_panel_row_bytes(code_of(bt.dtype), int(bt.shape[1]))) or row_bytes
+        row_bytes = int(_ffi.lib().spamd_sddmm_panel_row_bytes(sddmm_code(bt.dtype), int(bt.shape[1]))) or row_bytes
     if SDDMM_XCD_PANELS and int(bt.shape[0]) * row_bytes >= 8 * SDDMM_PANEL_BYTES:
         # XCD-private panels: a multiple of eight panels of at most 7/6 of the panel size (3.5 MiB), so that every XCD owns the same number
         # (measured at config 4: 16 panels of 6250 rows 0.357 ms private vs 0.390 shared; 17 panels of 6144 rows 0.402 vs 0.396)
@@ -1360,7 +1378,7 @@ def _sddmm_panels_into(panels, s_orig, s_data, a, bt, out):
         part = torch.empty(panels.count, dtype=out.dtype, device=out.device)     # (first-half sums, panel order)
         row_bytes = 512
     slots = _sddmm_row_slots(panels, row_bytes, panels.rows.element_size())
-    _ffi.call("spamd_sddmm_panels", code_of(a.dtype), code_of(out.dtype), code_of(panels.rows.dtype), panels.count,
+    _ffi.call("spamd_sddmm_panels", sddmm_code(a.dtype), code_of(out.dtype), code_of(panels.rows.dtype), panels.count,
               ptr(panels.rows), ptr(panels.cols), ptr(panels.pos), ptr(panels.values(s_orig, s_data)), ptr(a), a.stride(0),
               ptr(bt), bt.stride(0), int(a.shape[1]), slots, ptr(panels.xstate) if panels.xstate is not None else None,
               int(panels.xmax), ptr(part) if part is not None else None, ptr(out), stream_ptr(out.device))
@@ -1374,12 +1392,8 @@ def sddmm_coo(coords, s_data, a, bt, panels=None):
     nnz = int(s_data.numel())
     if a.dtype != bt.dtype:
         raise TypeError("a and bt must share a dtype")
-    if a.dtype == torch.bfloat16 or a.dtype == torch.float32:
-        sdt = torch.float32
-    elif a.dtype == torch.float64:
-        sdt = torch.float64
-    else:
-        raise TypeError(f"sddmm supports bfloat16/float32/float64 dense operands, got {a.dtype}")
+    in_code = sddmm_code(a.dtype)       # (TypeError for any other operand type)
+    sdt = torch.float64 if a.dtype == torch.float64 else torch.float32
     s_orig, s_data = s_data, s_data.to(sdt).contiguous()
     a, bt = a.contiguous(), bt.contiguous()
     if a.shape[1] != bt.shape[1]:
@@ -1400,7 +1414,7 @@ def sddmm_coo(coords, s_data, a, bt, panels=None):
     if panels is not None and nnz and panels.nnz == nnz and panels.count == nnz and sddmm_has_panels(a.dtype, a.shape[1]):
         _sddmm_panels_into(panels, s_orig, s_data, a, bt, out)
         return out
-    _ffi.call("spamd_sddmm", code_of(a.dtype), code_of(sdt), code_of(rows.dtype), nnz, ptr(rows), ptr(cols),
+    _ffi.call("spamd_sddmm", in_code, code_of(sdt), code_of(rows.dtype), nnz, ptr(rows), ptr(cols),
               ptr(s_data), ptr(a), a.stride(0), ptr(bt), bt.stride(0), int(a.shape[1]), ptr(out), stream_ptr(dev))
     return out
 
@@ -1453,12 +1467,13 @@ def sddmm_plan(coords, shape, threshold=None):
 
 
 def sddmm_coo_mfma(plan, coords, shape, s_data, a, bt, out=None, force=False, rest_panels=None):
-    """SDDMM with per-tile dispatch (bf16 operands): dense tiles on the matrix cores, the rest through the sampled
+    """SDDMM with per-tile dispatch (bf16 or float16 operands): dense tiles on the matrix cores, the rest through the sampled
     kernel (in column-panel order when `rest_panels` = sddmm_panels(..., subset=plan.rest) is given).  Returns None
     when the plan leaves (almost) everything to the sampled kernel and `force` is not set."""
     dev = require_hip(coords, s_data, a, bt)
-    if a.dtype != torch.bfloat16 or bt.dtype != torch.bfloat16:
-        raise TypeError("the matrix-core SDDMM path takes bfloat16 operands")
+    if a.dtype not in SDDMM_HALF_DTYPES or bt.dtype != a.dtype:
+        raise TypeError("the matrix-core SDDMM path takes bfloat16 or float16 operands, both of one type")
+    in_code = sddmm_code(a.dtype)
     Kd = int(a.shape[1])
     if Kd % 16 or Kd == 0:
         return None
@@ -1474,7 +1489,7 @@ def sddmm_coo_mfma(plan, coords, shape, s_data, a, bt, out=None, force=False, re
     if out is None:
         out = torch.empty(plan.nnz, dtype=torch.float32, device=dev)
     s = stream_ptr(dev)
-    _ffi.call("spamd_sddmm_mfma_tiles", code_of(rows.dtype), int(plan.tiles.numel()), ptr(plan.tiles), ptr(plan.seg_start),
+    _ffi.call("spamd_sddmm_mfma_tiles_typed", in_code, code_of(rows.dtype), int(plan.tiles.numel()), ptr(plan.tiles), ptr(plan.seg_start),
               ptr(plan.keys), ptr(plan.perm), plan.tile_cols, int(shape[0]), int(shape[1]), ptr(rows), ptr(cols), ptr(s_data),
               ptr(a), a.stride(0), ptr(bt), bt.stride(0), Kd, ptr(out), s)
     nrest = int(plan.rest.numel())
@@ -1484,9 +1499,47 @@ def sddmm_coo_mfma(plan, coords, shape, s_data, a, bt, out=None, force=False, re
     elif nrest:
         sub = torch.empty(nrest, dtype=torch.float32, device=dev)
         rr, cc, ss = gather(rows, plan.rest), gather(cols, plan.rest), gather(s_data, plan.rest)
-        _ffi.call("spamd_sddmm", code_of(a.dtype), code_of(torch.float32), code_of(rr.dtype), nrest, ptr(rr), ptr(cc), ptr(ss),
+        _ffi.call("spamd_sddmm", in_code, code_of(torch.float32), code_of(rr.dtype), nrest, ptr(rr), ptr(cc), ptr(ss),
                   ptr(a), a.stride(0), ptr(bt), bt.stride(0), Kd, ptr(sub), s)
         scatter_into(out, plan.rest, sub)
+    return out
+
+
+def sddmm_fold_strides(mask_lead, op_lead, what="a"):
+    """Per-axis strides of an operand's batch ordinal under an N-D mask: `mask_lead` = the mask's leading shape, `op_lead` =
+    the leading shape the operand HAS (right-aligned against it, NumPy's matmul rule - except that the mask's leading shape
+    is the result's, so an operand axis must be 1 or the mask's size and the operand may not have more axes).  A broadcast
+    axis has stride 0.  Returns (strides, number of batches of the operand)."""
+    mask_lead, op_lead = tuple(int(d) for d in mask_lead), tuple(int(d) for d in op_lead)
+    if len(op_lead) > len(mask_lead):
+        raise ValueError(f"sddmm: `{what}` has more leading axes {op_lead} than the mask {mask_lead}")
+    full = (1,) * (len(mask_lead) - len(op_lead)) + op_lead
+    strides, run = [0] * len(full), 1
+    for d in range(len(full) - 1, -1, -1):
+        if full[d] != 1 and full[d] != mask_lead[d]:
+            raise ValueError(f"sddmm: leading axes {op_lead} of `{what}` do not broadcast to the mask's {mask_lead}")
+        if full[d] != 1:
+            strides[d] = run
+            run *= full[d]
+    return strides, run
+
+
+def sddmm_fold(coords, nlead, a_strides, b_strides, M, N, rows_total, cols_total):
+    """[2, nnz] = (rows', cols') of an N-D mask's stored elements for the 2-D SDDMM kernels (csrc/sddmm_batch.hip): one launch,
+    int32 when `rows_total` = Ba * M and `cols_total` = Bb * N fit, else int64."""
+    dev = require_hip(coords)
+    coords = coords.contiguous()
+    if not index_dtype_ok(coords):
+        coords = coords.to(torch.int64)
+    nnz = int(coords.shape[1])
+    odt = torch.int32 if max(int(rows_total), int(cols_total)) < 2 ** 31 else torch.int64
+    out = torch.empty((2, nnz), dtype=odt, device=dev)       # [rows'; cols']: what the 2-D kernels take as `coords`
+    if nnz == 0:
+        return out
+    arr = _ct.c_int64 * max(int(nlead), 1)
+    _ffi.call("spamd_sddmm_batch_fold", code_of(coords.dtype), code_of(odt), int(nlead), nnz, ptr(coords), int(coords.stride(0)),
+              arr(*[int(x) for x in a_strides]), arr(*[int(x) for x in b_strides]), int(M), int(N), ptr(out[0]), ptr(out[1]),
+              stream_ptr(dev))
     return out
 
 

@@ -314,7 +314,7 @@ extern "C" int spamd_sddmm(int in_dtype, int s_dtype, int idx_dtype, int64_t nnz
 
 // 1 when K elements of in_dtype have a row-cached kernel (what spamd_sddmm_panels needs), else 0.
 extern "C" int spamd_sddmm_has_panels(int in_dtype, int64_t K) {
-  const int esz = in_dtype == SPAMD_BF16 ? 2 : (in_dtype == SPAMD_F32 ? 4 : (in_dtype == SPAMD_F64 ? 8 : 0));
+  const int esz = sd_elem_bytes(in_dtype);
   if (!esz || K <= 0 || (K * esz) % 16) return 0;
   const int64_t vecs = K * esz / 16;
   for (int L = 16; L <= 64; L <<= 1) {
@@ -341,11 +341,14 @@ static int sddmm_entry(int in_dtype, int s_dtype, int idx_dtype, int64_t nnz, co
   if (nnz == 0) return 0;
   if (((uintptr_t)A % 16) || ((uintptr_t)Bt % 16)) return SPAMD_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  const int esz = in_dtype == SPAMD_BF16 ? 2 : (in_dtype == SPAMD_F32 ? 4 : 8);
+  const int esz = in_dtype == SPAMD_BF16 || in_dtype == SPAMD_F16 ? 2 : (in_dtype == SPAMD_F32 ? 4 : 8);
   if ((lda * esz) % 16 || (ldb * esz) % 16) return SPAMD_EINVAL;
   SPAMD_DISPATCH_IDX(idx_dtype, I, {
     const I* r = (const I*)rows;
     const I* c = (const I*)cols;
+    if (in_dtype == SPAMD_F16 && s_dtype == SPAMD_F32)
+      return launch_sddmm<_Float16, float, I>(nnz, r, c, (const float*)s_data, (const _Float16*)A, lda, (const _Float16*)Bt,
+                                              ldb, K, (float*)out, st, perm, perm_chunk, xstate, xmax);
     if (in_dtype == SPAMD_BF16 && s_dtype == SPAMD_F32)
       return launch_sddmm<__hip_bfloat16, float, I>(nnz, r, c, (const float*)s_data, (const __hip_bfloat16*)A, lda,
                                                     (const __hip_bfloat16*)Bt, ldb, K, (float*)out, st, perm, perm_chunk, xstate, xmax);

@@ -6,6 +6,11 @@
 
 namespace spamd {
 
+// bytes of an element of the dense operands, 0 for a type the SDDMM kernels do not take
+inline int sd_elem_bytes(int in_dtype) {
+  return in_dtype == SPAMD_BF16 || in_dtype == SPAMD_F16 ? 2 : (in_dtype == SPAMD_F32 ? 4 : (in_dtype == SPAMD_F64 ? 8 : 0));
+}
+
 template <typename TIN>
 struct Acc { using type = float; };
 template <>
@@ -18,9 +23,17 @@ __device__ __forceinline__ typename Acc<TIN>::type to_acc(TIN x) {
 }
 
 typedef __bf16 sd_bf2 __attribute__((ext_vector_type(2)));
+typedef _Float16 sd_h2 __attribute__((ext_vector_type(2)));
+
+// float16 (TIN = _Float16) inner product of the row-cached / panel kernels: 1 = v_dot2c_f32_f16 (the bf16 form's twin),
+// 0 = v_cvt_f32_f16 + fused multiply-adds.  1 is kept: on MI355X the instruction keeps fp16 subnormal inputs and stays within
+// 2.2e-7 * sum|terms| of the float64 evaluation, like the other form (tests/test_sddmm_f16_gpu.py).
+#ifndef SD_F16_DOT2
+#define SD_F16_DOT2 1
+#endif
 
 // <a, b> over KS 16-byte vectors per lane.  bf16: v_dot2c_f32_bf16 (two products and the add per instruction, fp32
-// accumulate; no bf16 -> fp32 conversions); fp32/fp64: fused multiply-adds.
+// accumulate; no bf16 -> fp32 conversions); float16: see SD_F16_DOT2; fp32/fp64: fused multiply-adds.
 template <typename TIN, typename VT, int KS>
 __device__ __forceinline__ typename Acc<TIN>::type sd_dot(const VT (&av)[KS], const VT (&bv)[KS]) {
   using ACC = typename Acc<TIN>::type;
@@ -34,6 +47,15 @@ __device__ __forceinline__ typename Acc<TIN>::type sd_dot(const VT (&av)[KS], co
       __builtin_memcpy(b2, &bv[s], 16);
 #pragma unroll
       for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_fdot2_f32_bf16(a2[e], b2[e], acc, false);
+    }
+  } else if constexpr (std::is_same<TIN, _Float16>::value && SD_F16_DOT2) {
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      sd_h2 a2[4], b2[4];
+      __builtin_memcpy(a2, &av[s], 16);
+      __builtin_memcpy(b2, &bv[s], 16);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_fdot2(a2[e], b2[e], acc, false);
     }
   } else {
 #pragma unroll

@@ -15,6 +15,10 @@
 //         K-contiguous, so no LDS staging or transposition), K/16 MFMAs accumulate the tile in 16 VGPRs (fp32), the tile
 //         goes to LDS (32 x 33 floats per wave) and the tile's samples pick their element: out[n] = s[n] * P[i][j].
 //
+// float16 operands take the same kernels with v_mfma_f32_32x32x16_f16 (template parameter E; fragments, lane maps and cycles
+// are those of the bf16 form, and the bf16 instantiations compile to the code they compiled to before E existed).  fp16
+// subnormal operands are kept by that instruction (measured: tests/test_sddmm_f16_gpu.py).
+//
 // fp32 accumulate like the sampled kernel; the order of the K terms differs (the matrix core sums 16 products at a
 // time), so the two paths agree to ~K * 2^-24 * sum|a_k b_k|, not bit for bit (tests/test_sddmm_gpu.py).
 #include "common.h"
@@ -24,8 +28,18 @@ namespace spamd {
 
 constexpr int SD_TILE = 32;
 
-typedef __bf16 sd_bf16x8 __attribute__((ext_vector_type(8)));
 typedef float sd_f32x16 __attribute__((ext_vector_type(16)));
+
+// E = element type of the operands: __bf16 or _Float16.  An operand fragment is eight 16-bit elements per lane either way
+// (same lane map); E selects v_mfma_f32_32x32x16_bf16 or v_mfma_f32_32x32x16_f16 (the same cycles).
+template <typename E>
+using sd_frag = typename ExtVec<E, 8>::type;
+
+template <typename E>
+__device__ __forceinline__ sd_f32x16 sd_mfma(sd_frag<E> a, sd_frag<E> b, sd_f32x16 acc) {
+  if constexpr (std::is_same<E, _Float16>::value) return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, acc, 0, 0, 0);
+  else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
+}
 
 template <typename I>
 __global__ void __launch_bounds__(256) sddmm_tile_keys_kernel(int64_t nnz, const I* __restrict__ rows,
@@ -54,15 +68,16 @@ __global__ void __launch_bounds__(256) sddmm_classify_kernel(int64_t nseg, const
 }
 
 // One wave per dense tile.  tiles[d] = index of the tile's run in seg_start / position of its first sample.
-template <typename I>
+template <typename E, typename I>
 __global__ void __launch_bounds__(256) sddmm_mfma_kernel(int64_t ntiles, const int64_t* __restrict__ tiles,
                                                          const int64_t* __restrict__ seg_start,
                                                          const int64_t* __restrict__ keys_sorted,
                                                          const int64_t* __restrict__ perm, int64_t tile_cols, int64_t M,
                                                          int64_t N, const I* __restrict__ rows, const I* __restrict__ cols,
-                                                         const float* __restrict__ s_data, const __bf16* __restrict__ A,
-                                                         int64_t lda, const __bf16* __restrict__ Bt, int64_t ldb, int64_t K,
+                                                         const float* __restrict__ s_data, const E* __restrict__ A,
+                                                         int64_t lda, const E* __restrict__ Bt, int64_t ldb, int64_t K,
                                                          float* __restrict__ out) {
+  using sd_x8 = sd_frag<E>;
   __shared__ float tile_lds[4][SD_TILE][SD_TILE + 1];
   const int lane = threadIdx.x & 63;
   const int wv = threadIdx.x >> 6;
@@ -75,26 +90,26 @@ __global__ void __launch_bounds__(256) sddmm_mfma_kernel(int64_t ntiles, const i
   int64_t ar = tr * SD_TILE + (lane & 31), bc = tc * SD_TILE + (lane & 31);
   if (ar >= M) ar = M - 1;  // edge tiles: clamped rows feed elements no sample refers to
   if (bc >= N) bc = N - 1;
-  const __bf16* ap = A + ar * lda + (lane >> 5) * 8;
-  const __bf16* bp = Bt + bc * ldb + (lane >> 5) * 8;
+  const E* ap = A + ar * lda + (lane >> 5) * 8;
+  const E* bp = Bt + bc * ldb + (lane >> 5) * 8;
   sd_f32x16 acc;
 #pragma unroll
   for (int v = 0; v < 16; ++v) acc[v] = 0.f;
   // K is a multiple of 16 (checked by the caller); four k-steps of loads in flight before their MFMAs
   int64_t k = 0;
   for (; k + 64 <= K; k += 64) {
-    sd_bf16x8 a0 = *reinterpret_cast<const sd_bf16x8*>(ap + k), b0 = *reinterpret_cast<const sd_bf16x8*>(bp + k);
-    sd_bf16x8 a1 = *reinterpret_cast<const sd_bf16x8*>(ap + k + 16), b1 = *reinterpret_cast<const sd_bf16x8*>(bp + k + 16);
-    sd_bf16x8 a2 = *reinterpret_cast<const sd_bf16x8*>(ap + k + 32), b2 = *reinterpret_cast<const sd_bf16x8*>(bp + k + 32);
-    sd_bf16x8 a3 = *reinterpret_cast<const sd_bf16x8*>(ap + k + 48), b3 = *reinterpret_cast<const sd_bf16x8*>(bp + k + 48);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b2, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, b3, acc, 0, 0, 0);
+    sd_x8 a0 = *reinterpret_cast<const sd_x8*>(ap + k), b0 = *reinterpret_cast<const sd_x8*>(bp + k);
+    sd_x8 a1 = *reinterpret_cast<const sd_x8*>(ap + k + 16), b1 = *reinterpret_cast<const sd_x8*>(bp + k + 16);
+    sd_x8 a2 = *reinterpret_cast<const sd_x8*>(ap + k + 32), b2 = *reinterpret_cast<const sd_x8*>(bp + k + 32);
+    sd_x8 a3 = *reinterpret_cast<const sd_x8*>(ap + k + 48), b3 = *reinterpret_cast<const sd_x8*>(bp + k + 48);
+    acc = sd_mfma<E>(a0, b0, acc);
+    acc = sd_mfma<E>(a1, b1, acc);
+    acc = sd_mfma<E>(a2, b2, acc);
+    acc = sd_mfma<E>(a3, b3, acc);
   }
   for (; k < K; k += 16) {
-    sd_bf16x8 a0 = *reinterpret_cast<const sd_bf16x8*>(ap + k), b0 = *reinterpret_cast<const sd_bf16x8*>(bp + k);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc, 0, 0, 0);
+    sd_x8 a0 = *reinterpret_cast<const sd_x8*>(ap + k), b0 = *reinterpret_cast<const sd_x8*>(bp + k);
+    acc = sd_mfma<E>(a0, b0, acc);
   }
   // D[i][j]: j = lane % 32, i = (v % 4) + 8 * (v / 4) + 4 * (lane / 32)
   float(*P)[SD_TILE + 1] = tile_lds[wv];
@@ -116,22 +131,23 @@ __global__ void __launch_bounds__(256) sddmm_mfma_kernel(int64_t ntiles, const i
 // i.e. 16 KB instead of 32 KB per tile at K = 256 (the tile kernel is bound by fetching its panels, not by the MFMAs).
 constexpr int SD_GROUP = 4;
 
-template <typename I, int KS>
+template <typename E, typename I, int KS>
 __global__ void __launch_bounds__(256) sddmm_mfma_rowreuse_kernel(int64_t ntiles, const int64_t* __restrict__ tiles,
                                                                   const int64_t* __restrict__ seg_start,
                                                                   const int64_t* __restrict__ keys_sorted,
                                                                   const int64_t* __restrict__ perm, int64_t tile_cols, int64_t M,
                                                                   int64_t N, const I* __restrict__ rows,
                                                                   const I* __restrict__ cols, const float* __restrict__ s_data,
-                                                                  const __bf16* __restrict__ A, int64_t lda,
-                                                                  const __bf16* __restrict__ Bt, int64_t ldb,
+                                                                  const E* __restrict__ A, int64_t lda,
+                                                                  const E* __restrict__ Bt, int64_t ldb,
                                                                   float* __restrict__ out) {
+  using sd_x8 = sd_frag<E>;
   __shared__ float tile_lds[4][SD_TILE][SD_TILE + 1];
   const int lane = threadIdx.x & 63;
   const int wv = threadIdx.x >> 6;
   float(*P)[SD_TILE + 1] = tile_lds[wv];
   const int64_t d0 = ((int64_t)blockIdx.x * 4 + wv) * SD_GROUP;
-  sd_bf16x8 areg[KS];
+  sd_x8 areg[KS];
   int64_t cur_tr = -1;
   for (int g = 0; g < SD_GROUP; ++g) {
     const int64_t d = d0 + g;
@@ -143,25 +159,25 @@ __global__ void __launch_bounds__(256) sddmm_mfma_rowreuse_kernel(int64_t ntiles
     if (tr != cur_tr) {
       int64_t ar = tr * SD_TILE + (lane & 31);
       if (ar >= M) ar = M - 1;
-      const __bf16* ap = A + ar * lda + (lane >> 5) * 8;
+      const E* ap = A + ar * lda + (lane >> 5) * 8;
 #pragma unroll
-      for (int q = 0; q < KS; ++q) areg[q] = *reinterpret_cast<const sd_bf16x8*>(ap + q * 16);
+      for (int q = 0; q < KS; ++q) areg[q] = *reinterpret_cast<const sd_x8*>(ap + q * 16);
       cur_tr = tr;
     }
     int64_t bc = tc * SD_TILE + (lane & 31);
     if (bc >= N) bc = N - 1;
-    const __bf16* bp = Bt + bc * ldb + (lane >> 5) * 8;
+    const E* bp = Bt + bc * ldb + (lane >> 5) * 8;
     sd_f32x16 acc;
 #pragma unroll
     for (int v = 0; v < 16; ++v) acc[v] = 0.f;
 #pragma unroll
     for (int q0 = 0; q0 < KS; q0 += 4) {
-      sd_bf16x8 b0 = *reinterpret_cast<const sd_bf16x8*>(bp + q0 * 16), b1 = *reinterpret_cast<const sd_bf16x8*>(bp + q0 * 16 + 16);
-      sd_bf16x8 b2 = *reinterpret_cast<const sd_bf16x8*>(bp + q0 * 16 + 32), b3 = *reinterpret_cast<const sd_bf16x8*>(bp + q0 * 16 + 48);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(areg[q0], b0, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(areg[q0 + 1], b1, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(areg[q0 + 2], b2, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(areg[q0 + 3], b3, acc, 0, 0, 0);
+      sd_x8 b0 = *reinterpret_cast<const sd_x8*>(bp + q0 * 16), b1 = *reinterpret_cast<const sd_x8*>(bp + q0 * 16 + 16);
+      sd_x8 b2 = *reinterpret_cast<const sd_x8*>(bp + q0 * 16 + 32), b3 = *reinterpret_cast<const sd_x8*>(bp + q0 * 16 + 48);
+      acc = sd_mfma<E>(areg[q0], b0, acc);
+      acc = sd_mfma<E>(areg[q0 + 1], b1, acc);
+      acc = sd_mfma<E>(areg[q0 + 2], b2, acc);
+      acc = sd_mfma<E>(areg[q0 + 3], b3, acc);
     }
 #pragma unroll
     for (int v = 0; v < 16; ++v) P[(v & 3) + 8 * (v >> 2) + 4 * (lane >> 5)][lane & 31] = acc[v];
@@ -208,18 +224,16 @@ extern "C" int spamd_sddmm_tile_classify(int64_t nseg, const int64_t* seg_start,
   return launch_status();
 }
 
-extern "C" int spamd_sddmm_mfma_tiles(int idx_dtype, int64_t ntiles, const int64_t* tiles, const int64_t* seg_start,
-                                      const int64_t* keys_sorted, const int64_t* perm, int64_t tile_cols, int64_t M, int64_t N,
-                                      const void* rows, const void* cols, const float* s_data, const void* A, int64_t lda,
-                                      const void* Bt, int64_t ldb, int64_t K, float* out, void* stream) {
-  if (ntiles < 0 || K <= 0 || K % 16 != 0 || M <= 0 || N <= 0 || tile_cols <= 0) return SPAMD_EINVAL;
-  if (ntiles == 0) return 0;
-  if (((uintptr_t)A % 16) || ((uintptr_t)Bt % 16) || ((lda * 2) % 16) || ((ldb * 2) % 16)) return SPAMD_EINVAL;
+template <typename E>
+static int launch_mfma_tiles(int idx_dtype, int64_t ntiles, const int64_t* tiles, const int64_t* seg_start,
+                             const int64_t* keys_sorted, const int64_t* perm, int64_t tile_cols, int64_t M, int64_t N,
+                             const void* rows, const void* cols, const float* s_data, const void* A, int64_t lda,
+                             const void* Bt, int64_t ldb, int64_t K, float* out, void* stream) {
 #define SD_ROWREUSE(KS)                                                                                                    \
   SPAMD_DISPATCH_IDX(idx_dtype, I,                                                                                          \
-                     hipLaunchKernelGGL((sddmm_mfma_rowreuse_kernel<I, KS>), dim3((unsigned)ceil_div(ntiles, (int64_t)(4 * SD_GROUP))), \
+                     hipLaunchKernelGGL((sddmm_mfma_rowreuse_kernel<E, I, KS>), dim3((unsigned)ceil_div(ntiles, (int64_t)(4 * SD_GROUP))), \
                                         dim3(256), 0, (hipStream_t)stream, ntiles, tiles, seg_start, keys_sorted, perm, tile_cols, \
-                                        M, N, (const I*)rows, (const I*)cols, s_data, (const __bf16*)A, lda, (const __bf16*)Bt,  \
+                                        M, N, (const I*)rows, (const I*)cols, s_data, (const E*)A, lda, (const E*)Bt,  \
                                         ldb, out))                                                                          \
   return launch_status();
   if (ntiles >= 4 * SD_GROUP * 1024) {   // (a short tile list fills the chip better with one wave per tile)
@@ -229,9 +243,34 @@ extern "C" int spamd_sddmm_mfma_tiles(int idx_dtype, int64_t ntiles, const int64
   }
 #undef SD_ROWREUSE
   SPAMD_DISPATCH_IDX(idx_dtype, I,
-                     hipLaunchKernelGGL(sddmm_mfma_kernel<I>, dim3((unsigned)ceil_div(ntiles, (int64_t)4)), dim3(256), 0,
+                     hipLaunchKernelGGL((sddmm_mfma_kernel<E, I>), dim3((unsigned)ceil_div(ntiles, (int64_t)4)), dim3(256), 0,
                                         (hipStream_t)stream, ntiles, tiles, seg_start, keys_sorted, perm, tile_cols, M, N,
-                                        (const I*)rows, (const I*)cols, s_data, (const __bf16*)A, lda, (const __bf16*)Bt, ldb,
+                                        (const I*)rows, (const I*)cols, s_data, (const E*)A, lda, (const E*)Bt, ldb,
                                         K, out))
   return launch_status();
+}
+
+extern "C" int spamd_sddmm_mfma_tiles_typed(int in_dtype, int idx_dtype, int64_t ntiles, const int64_t* tiles,
+                                            const int64_t* seg_start, const int64_t* keys_sorted, const int64_t* perm,
+                                            int64_t tile_cols, int64_t M, int64_t N, const void* rows, const void* cols,
+                                            const float* s_data, const void* A, int64_t lda, const void* Bt, int64_t ldb,
+                                            int64_t K, float* out, void* stream) {
+  if (in_dtype != SPAMD_BF16 && in_dtype != SPAMD_F16) return SPAMD_EINVAL;   // the matrix-core path has 16-bit kernels only
+  if (ntiles < 0 || K <= 0 || K % 16 != 0 || M <= 0 || N <= 0 || tile_cols <= 0) return SPAMD_EINVAL;
+  if (ntiles == 0) return 0;
+  if (((uintptr_t)A % 16) || ((uintptr_t)Bt % 16) || ((lda * 2) % 16) || ((ldb * 2) % 16)) return SPAMD_EINVAL;
+  if (in_dtype == SPAMD_F16)
+    return launch_mfma_tiles<_Float16>(idx_dtype, ntiles, tiles, seg_start, keys_sorted, perm, tile_cols, M, N, rows, cols, s_data,
+                                       A, lda, Bt, ldb, K, out, stream);
+  return launch_mfma_tiles<__bf16>(idx_dtype, ntiles, tiles, seg_start, keys_sorted, perm, tile_cols, M, N, rows, cols, s_data, A,
+                                   lda, Bt, ldb, K, out, stream);
+}
+
+// the bfloat16 form (the entry point as it was before float16 operands)
+extern "C" int spamd_sddmm_mfma_tiles(int idx_dtype, int64_t ntiles, const int64_t* tiles, const int64_t* seg_start,
+                                      const int64_t* keys_sorted, const int64_t* perm, int64_t tile_cols, int64_t M, int64_t N,
+                                      const void* rows, const void* cols, const float* s_data, const void* A, int64_t lda,
+                                      const void* Bt, int64_t ldb, int64_t K, float* out, void* stream) {
+  return spamd_sddmm_mfma_tiles_typed(SPAMD_BF16, idx_dtype, ntiles, tiles, seg_start, keys_sorted, perm, tile_cols, M, N, rows,
+                                      cols, s_data, A, lda, Bt, ldb, K, out, stream);
 }

@@ -377,7 +377,7 @@ int sddmm_rowcache_panels(int in_dtype, int s_dtype, int idx_dtype, int64_t nnz,
 // second half and writes s * sum to the element's place.  spamd_sddmm's row-major kernel adds its halves in the same
 // order (sd_dot_1k), so the two orders stay bit-identical.
 extern "C" int64_t spamd_sddmm_panel_row_bytes(int in_dtype, int64_t K) {
-  const int esz = in_dtype == SPAMD_BF16 ? 2 : (in_dtype == SPAMD_F32 ? 4 : (in_dtype == SPAMD_F64 ? 8 : 0));
+  const int esz = sd_elem_bytes(in_dtype);
   if (!esz || K <= 0) return 0;
   return K * esz == 1024 ? 512 : K * esz;
 }
@@ -389,7 +389,7 @@ extern "C" int spamd_sddmm_panels(int in_dtype, int s_dtype, int idx_dtype, int6
   if (!perm || (xcd_first && xcd_max < 0) || nnz < 0 || K <= 0) return SPAMD_EINVAL;
   if (nnz == 0) return 0;
   if (((uintptr_t)A % 16) || ((uintptr_t)Bt % 16)) return SPAMD_EINVAL;
-  const int esz = in_dtype == SPAMD_BF16 ? 2 : (in_dtype == SPAMD_F32 ? 4 : (in_dtype == SPAMD_F64 ? 8 : 0));
+  const int esz = sd_elem_bytes(in_dtype);
   if (!esz) return SPAMD_ETYPE;
   if ((lda * esz) % 16 || (ldb * esz) % 16 || (K * esz) % 16) return SPAMD_EINVAL;
   // Rows of 1 KB and more (fp32 K = 256, ...): the distinct A rows of a workgroup no longer fit LDS at an occupancy that
@@ -408,6 +408,9 @@ extern "C" int spamd_sddmm_panels(int in_dtype, int s_dtype, int idx_dtype, int6
         return launch_panel_halves<__hip_bfloat16, float, I>(nnz, r, c, (const float*)s_p, (const __hip_bfloat16*)A, lda,
                                                              (const __hip_bfloat16*)Bt, ldb, K, (float*)out, st, perm, chunk,
                                                              xcd_first, xcd_max, (float*)part);
+      if (in_dtype == SPAMD_F16 && s_dtype == SPAMD_F32)
+        return launch_panel_halves<_Float16, float, I>(nnz, r, c, (const float*)s_p, (const _Float16*)A, lda, (const _Float16*)Bt,
+                                                       ldb, K, (float*)out, st, perm, chunk, xcd_first, xcd_max, (float*)part);
       if (in_dtype == SPAMD_F32 && s_dtype == SPAMD_F32)
         return launch_panel_halves<float, float, I>(nnz, r, c, (const float*)s_p, (const float*)A, lda, (const float*)Bt, ldb, K,
                                                     (float*)out, st, perm, chunk, xcd_first, xcd_max, (float*)part);
@@ -423,6 +426,9 @@ extern "C" int spamd_sddmm_panels(int in_dtype, int s_dtype, int idx_dtype, int6
     if (in_dtype == SPAMD_BF16 && s_dtype == SPAMD_F32)
       return launch_panel<__hip_bfloat16, float, I>(nnz, r, c, (const float*)s_p, (const __hip_bfloat16*)A, lda,
                                                     (const __hip_bfloat16*)Bt, ldb, K, (float*)out, st, perm, chunk, xcd_first, xcd_max);
+    if (in_dtype == SPAMD_F16 && s_dtype == SPAMD_F32)
+      return launch_panel<_Float16, float, I>(nnz, r, c, (const float*)s_p, (const _Float16*)A, lda, (const _Float16*)Bt, ldb, K,
+                                              (float*)out, st, perm, chunk, xcd_first, xcd_max);
     if (in_dtype == SPAMD_F32 && s_dtype == SPAMD_F32)
       return launch_panel<float, float, I>(nnz, r, c, (const float*)s_p, (const float*)A, lda, (const float*)Bt, ldb, K,
                                            (float*)out, st, perm, chunk, xcd_first, xcd_max);
