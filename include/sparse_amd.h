@@ -34,8 +34,8 @@ extern "C" {
 #define SPAMD_BF16 4
 #define SPAMD_U8 5 /* bool (0/1) — results of comparisons, any/all, astype(bool) */
 #define SPAMD_C64 6  /* complex64: interleaved (re, im) float32 pairs - the products (spamd_spmm_csr_complex, spamd_spgemm_expand,
-                      * spamd_segment_reduce with op = add) and the complex elementwise / reduction entry points (spamd_cplx_*,
-                      * spamd_merge_union_complex) */
+                      * spamd_segment_reduce with op = add), the complex elementwise / reduction entry points (spamd_cplx_*,
+                      * spamd_merge_union_complex) and the complex SDDMM (spamd_sddmm_complex) */
 #define SPAMD_C128 7 /* complex128: interleaved (re, im) float64 pairs - the same entry points */
 #define SPAMD_F16 8  /* IEEE float16: dense operands of the SDDMM entry points only (spamd_sddmm, spamd_sddmm_panels,
                       * spamd_sddmm_mfma_tiles_typed) */
@@ -656,6 +656,21 @@ int spamd_sddmm_mfma_tiles_typed(int in_dtype, int idx_dtype, int64_t ntiles, co
 int spamd_sddmm_batch_fold(int idx_dtype, int out_dtype, int nlead, int64_t nnz, const void* coords, int64_t ldc,
                            const int64_t* a_strides, const int64_t* b_strides, int64_t M, int64_t N, void* rows, void* cols,
                            void* stream);
+
+/* A9 with complex operands (csrc/sddmm_complex.hip): val_dtype C64 | C128 is the type of s_data, A, Bt and out alike, the
+ * product is the reference's `s * (a @ b)` (examples/sddmm_example.py:51-52) without conjugation, complex64 accumulates in
+ * fp32 and complex128 in fp64.  lda / ldb are in complex elements; A, Bt and their row pitches are 16-byte aligned.
+ * perm == NULL: the mask's own order, out[n] = s_data[n] * <A[rows[n]], Bt[cols[n]]>.  perm != NULL: the column-panel
+ * order of spamd_sddmm_panels - rows / cols / s_data in panel order, out[perm[n]] = ..., lane groups taking perm_chunk
+ * elements per turn (<= 0: default), xstate / xmax = xcd_first / xcd_max (NULL / 0: all XCDs share every panel) - with
+ * the same bits as the mask's own order.  Rows that have a row-cached kernel (spamd_sddmm_complex_has_rowcache: 16-byte
+ * vectors = L * KS, L in 16 | 32 | 64, KS in 1..4) take it, every other K the gather kernel; SPAMD_EINVAL when perm is
+ * given for a K without the row-cached kernel.  Returns before any launch: 0 for nnz == 0, SPAMD_ETYPE for any other
+ * value or index code, SPAMD_EINVAL for negative sizes and misaligned operands or pitches. */
+int spamd_sddmm_complex(int val_dtype, int idx_dtype, int64_t nnz, const void* rows, const void* cols, const void* s_data,
+                        const void* A, int64_t lda, const void* Bt, int64_t ldb, int64_t K, void* out, const int64_t* perm,
+                        int64_t perm_chunk, const int64_t* xstate, int64_t xmax, void* stream);
+int spamd_sddmm_complex_has_rowcache(int val_dtype, int64_t K); /* 1: rows of K complex values have the row-cached kernel */
 
 /* =======================================================================================
  * A11  Complex elementwise functions, conversions and reductions (val_dtype C64 | C128; SPAMD_ETYPE otherwise)

@@ -40,6 +40,12 @@ def sddmm(s, a, b=None, *, bt=None):
     or float16/float32/float64 ndarrays, both of one type (16-bit and fp32 operands accumulate in
     fp32 and give float32 values).  Result has the format of `s`, zeros pruned.
 
+    Complex operands - both complex64 (fp32 accumulation) or both complex128 - give values of their own type:
+    `s * (a @ b)` without conjugation, the mask values (real, integer, bool or complex) converted to that type on the
+    device.  Complex mask values over float32 / float64 operands multiply the real sampled product and give complex64 /
+    complex128; over 16-bit operands they are refused (TypeError).  Complex rows run through the gather and row-cached
+    kernels only (csrc/sddmm_complex.hip): no matrix-core tiles, no inner-dimension padding.
+
     `s` may have more than two dimensions: `a` is (..., M, K), `b` (..., K, N) or `bt` (..., N, K), and
     their leading axes broadcast against the leading axes of `s.shape` (NumPy's matmul rule, except that
     the mask's leading shape is the result's: an operand axis is 1 or the mask's size).  The whole stack
@@ -92,6 +98,13 @@ def sddmm(s, a, b=None, *, bt=None):
             plans[key] = K.sddmm_panels(coords, shape2, width, subset=subset)
         return plans[key]
 
+    mask_vals = sc.data
+    if mask_vals.is_complex() and not at.is_complex():
+        # complex mask values over real operands: the real dot products under a unit mask through the routes below, then one
+        # device multiply by the mask values in the complex type of the operands' precision
+        if at.dtype not in (torch.float32, torch.float64) or btt.dtype != at.dtype:
+            raise TypeError(f"sddmm: complex mask values need float32/float64 or complex operands, got {at.dtype} and {btt.dtype}")
+        mask_vals = torch.ones(sc.nnz, dtype=at.dtype, device=sc.device)     # (memory plumbing: the unit mask)
     vals = None
     if at.dtype in K.SDDMM_HALF_DTYPES and btt.dtype == at.dtype and sc.nnz >= K.SDDMM_TILE_THRESHOLD and at.shape[1] % 16 == 0:
         key = ("tiles", K.SDDMM_TILE_THRESHOLD)
@@ -111,8 +124,13 @@ def sddmm(s, a, b=None, *, bt=None):
                 rest = plans[key]
             vals = K.sddmm_coo_mfma(plan, coords, shape2, sc.data, at, btt, force=True, rest_panels=rest)
     if vals is None:
-        vals = K.sddmm_coo(coords, sc.data, at, btt,
+        vals = K.sddmm_coo(coords, mask_vals, at, btt,
                            panels=panels_of(None, "all") if K.sddmm_panels_pay(sc.nnz, at, btt, width) else None)
+    if mask_vals is not sc.data:
+        from ._umath import binary_arrays
+
+        ct = torch.complex128 if at.dtype == torch.float64 else torch.complex64
+        vals = binary_arrays("multiply", K.convert(sc.data, ct), K.convert(vals, ct))
     out = COO(sc.coords, vals, shape=s.shape, has_duplicates=False, sorted=True, prune=True)
     return out.asformat("gcxs", compressed_axes=s.compressed_axes) if out_gcxs else out
 

@@ -307,7 +307,8 @@ def sharded_spgemm(a_local, b_shard, group=None):
 
 def sharded_sddmm(s_local, a_local, bt_shard, n_cols, group=None):
     """out_local = sddmm(S_local, A_local, all_gather(Bt)): mask rows and A rows co-sharded,
-    Bt (N x K) row-sharded and gathered once."""
+    Bt (N x K) row-sharded and gathered once.  The operands are forwarded to `sddmm` as they are: complex64 / complex128
+    operands pass through (the sharded form has no test of its own for them)."""
     from . import _api
 
     bt = gathered_rows(bt_shard, n_cols, group)

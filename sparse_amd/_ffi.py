@@ -110,7 +110,9 @@ SIGNATURES = {
     "spamd_sddmm_mfma_tiles_typed": (_int, [_int, _int, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp,
                                             _i64, _i64, _vp, _vp]),
     "spamd_sddmm_batch_fold": (_int, [_int, _int, _int, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
-    "spamd_merge_num_blocks": (_i64, [_i64, _i64]),
+    "spamd_sddmm_complex": (_int, [_int, _int, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _vp]),
+    "spamd_sddmm_complex_has_rowcache": (_int, [_int, _i64]),
+    "spamd_merge_num_blocks":(_i64, [_i64, _i64]),
     "spamd_merge_partition": (_int, [_i64, _vp, _i64, _vp, _vp, _vp]),
     "spamd_merge_union": (_int, [_int, _int, _int, _i64, _vp, _vp, _i64, _vp, _vp, _C.c_uint64, _C.c_uint64,
                                  _C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp]),

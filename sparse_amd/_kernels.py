@@ -1229,9 +1229,22 @@ def sddmm_code(dt):
     return _ffi.F16 if dt is torch.float16 else code_of(dt)
 
 
+def sddmm_complex_code(dt):
+    """C-ABI code of a complex SDDMM operand type (`spamd_sddmm_complex`): complex64 / complex128 and nothing else.  A lookup
+    of its own, next to `product_code` and `sddmm_code`: `SDDMM_DTYPES` stays the list of the real kernels' types."""
+    dt = dt if isinstance(dt, torch.dtype) else torch_dtype(dt)
+    if dt not in _COMPLEX_CODE:
+        raise TypeError(f"complex sddmm supports complex64/complex128 dense operands, got {dt}")
+    return _COMPLEX_CODE[dt]
+
+
 def sddmm_has_panels(dtype, Kd):
-    """Does spamd_sddmm_panels have a kernel for rows of `Kd` elements of `dtype`?"""
+    """Does the column-panel order have a kernel for rows of `Kd` elements of `dtype` (spamd_sddmm_panels; for complex types
+    the row-cached kernel of spamd_sddmm_complex)?"""
     try:
+        dtype = dtype if isinstance(dtype, torch.dtype) else torch_dtype(dtype)
+        if dtype in _COMPLEX_CODE:
+            return bool(_ffi.lib().spamd_sddmm_complex_has_rowcache(_COMPLEX_CODE[dtype], int(Kd)))
         code = sddmm_code(dtype)
     except (TypeError, KeyError):
         return False
@@ -1268,7 +1281,7 @@ def sddmm_panel_width(bt):
         return 0
     if not sddmm_has_panels(bt.dtype, bt.shape[1]):
         return 0
-    if SDDMM_TWO_PASS:
+    if SDDMM_TWO_PASS and not bt.is_complex():
         # rows of 1 KB run as two passes over 512-byte halves (round 5): a panel is sized for the half-rows
         row_bytes = int(_ffi.lib().spamd_sddmm_panel_row_bytes(sddmm_code(bt.dtype), int(bt.shape[1]))) or row_bytes
     if SDDMM_XCD_PANELS and int(bt.shape[0]) * row_bytes >= 8 * SDDMM_PANEL_BYTES:
@@ -1372,6 +1385,13 @@ def _sddmm_row_slots(panels, row_bytes, idx_bytes):
 
 def _sddmm_panels_into(panels, s_orig, s_data, a, bt, out):
     """The elements of `panels` (all of the mask or a subset), written to their positions in `out`."""
+    if a.is_complex():
+        # the row-cached kernel in panel order for every row length it has: no half-row passes, no LDS slots
+        _ffi.call("spamd_sddmm_complex", sddmm_complex_code(a.dtype), code_of(panels.rows.dtype), panels.count, ptr(panels.rows),
+                  ptr(panels.cols), ptr(panels.values(s_orig, s_data)), ptr(a), a.stride(0), ptr(bt), bt.stride(0),
+                  int(a.shape[1]), ptr(out), ptr(panels.pos), int(panels.chunk),
+                  ptr(panels.xstate) if panels.xstate is not None else None, int(panels.xmax), stream_ptr(out.device))
+        return
     part = None
     row_bytes = int(a.shape[1]) * a.element_size()
     if SDDMM_TWO_PASS and row_bytes == 1024:
@@ -1392,9 +1412,17 @@ def sddmm_coo(coords, s_data, a, bt, panels=None):
     nnz = int(s_data.numel())
     if a.dtype != bt.dtype:
         raise TypeError("a and bt must share a dtype")
-    in_code = sddmm_code(a.dtype)       # (TypeError for any other operand type)
-    sdt = torch.float64 if a.dtype == torch.float64 else torch.float32
-    s_orig, s_data = s_data, s_data.to(sdt).contiguous()
+    cplx = a.is_complex()
+    in_code = sddmm_complex_code(a.dtype) if cplx else sddmm_code(a.dtype)       # (TypeError for any other operand type)
+    if cplx:
+        # mask values of any real or complex type become the operands' complex type on the device (spamd_cplx_convert)
+        sdt = a.dtype
+        s_orig, s_data = s_data, convert(s_data.contiguous(), sdt).contiguous()
+    else:
+        if s_data.is_complex():
+            raise TypeError("complex mask values over real operands: multiply the unit-mask product by them (sparse_amd.sddmm does)")
+        sdt = torch.float64 if a.dtype == torch.float64 else torch.float32
+        s_orig, s_data = s_data, s_data.to(sdt).contiguous()
     a, bt = a.contiguous(), bt.contiguous()
     if a.shape[1] != bt.shape[1]:
         raise ValueError("shape-mismatch for sum")
@@ -1413,6 +1441,10 @@ def sddmm_coo(coords, s_data, a, bt, panels=None):
     out = torch.empty(nnz, dtype=sdt, device=dev)
     if panels is not None and nnz and panels.nnz == nnz and panels.count == nnz and sddmm_has_panels(a.dtype, a.shape[1]):
         _sddmm_panels_into(panels, s_orig, s_data, a, bt, out)
+        return out
+    if cplx:
+        _ffi.call("spamd_sddmm_complex", in_code, code_of(rows.dtype), nnz, ptr(rows), ptr(cols), ptr(s_data), ptr(a), a.stride(0),
+                  ptr(bt), bt.stride(0), int(a.shape[1]), ptr(out), None, 0, None, 0, stream_ptr(dev))
         return out
     _ffi.call("spamd_sddmm", in_code, code_of(sdt), code_of(rows.dtype), nnz, ptr(rows), ptr(cols),
               ptr(s_data), ptr(a), a.stride(0), ptr(bt), bt.stride(0), int(a.shape[1]), ptr(out), stream_ptr(dev))
