@@ -60,7 +60,9 @@ def _compressed_axis_slice(x, index):
         from ._coo import COO
 
         return COO(indices[None, :], data, shape=(x.shape[1 - ca],), has_duplicates=False, fill_value=x.fill_value).asformat("gcxs")
-    indptr = x.indptr[a:b + 1].clone()
+    # (an empty range `x[a:a]` holds one pointer, and it is zero whatever `indptr[a]` is: `indptr[0] == 0` is what
+    # `_concatenate_compressed` and the sharded products' `[indptr[0], indptr[-1])` reading assume)
+    indptr = x.indptr[a:b + 1].clone() if b > a else torch.zeros(1, dtype=x.indptr.dtype, device=x.indptr.device)
     if p0:
         from ._umath import binary_arrays
 
