@@ -725,6 +725,34 @@ int spamd_cplx_segment_reduce(int op, int val_dtype, int64_t n, const void* data
 int64_t spamd_cplx_sum_long_ws_bytes(int64_t m);
 int spamd_cplx_sum_long(int val_dtype, int64_t m, const void* run, void* out, void* ws, int64_t ws_bytes, void* stream);
 
+/* =======================================================================================
+ * A12  MTTKRP: matricised tensor times Khatri-Rao product (csrc/mttkrp.hip) - the reference's
+ *   sparse.sum(B[:, :, :, None] * D[None, None, :, :] * C[None, :, None, :], axis=(1, 2))   (examples/mttkrp_example.py)
+ *   for any mode of an N-D COO tensor, 2 <= ndim <= 8, without the two broadcast intermediates:
+ *     out[i, r] = sum over stored elements n with coords[mode][n] == i of data[n] * prod_{d != mode} U_d[coords[d][n], r]
+ *   val_dtype F32 | F64 is the type of data, every factor, the workspace and out; idx_dtype I32 | I64 the type of coords
+ *   ([ndim, nnz], row pitch ldc elements, read at that width).  factors / pitches: HOST arrays of ndim device pointers and
+ *   row pitches in elements (>= R); the entries at `mode` are ignored.  The plan groups the stored elements by
+ *   coords[mode]: rowptr (int64[nrows + 1], nrows = shape[mode]) bounds row i's positions in plan order, perm (int64[nnz])
+ *   maps a plan position to a stored position, NULL = the stored order (mode 0 of a canonical COO).
+ *   Contract (same spirit as spamd_spmm_csr): every out element is written exactly once, by one lane; no atomics; results
+ *   are bitwise reproducible and do not depend on the launch geometry.
+ *     a term   t = data[n]; for d ascending, d != mode: t = t * U_d[coords[d][n], r], every product rounded
+ *     a row    its elements, in plan order, are cut into pieces of `chunk` elements; a piece is summed sequentially from
+ *              +0.0 and the piece sums are added in piece order (a row of at most `chunk` elements: one sequential sum;
+ *              an empty row: +0.0)
+ *   flags: SPAMD_EXACT_MULADD rounds every multiply and add separately; without it the last multiply of a term and the
+ *   accumulate are one fma.  ws: spamd_mttkrp_ws_bytes(val_dtype, nnz, R, chunk) bytes (0 when nnz <= chunk; SPAMD_EWS
+ *   when smaller).  out: nrows rows of pitch ldo >= R elements.
+ *   Returns before any launch: SPAMD_ETYPE for other type codes, SPAMD_EINVAL for negative sizes, ndim outside 2..8, mode
+ *   outside 0..ndim-1, a pitch below R or chunk < 1, 0 for R == 0 or nrows == 0; nnz == 0 zero-fills out and returns 0.
+ * ------------------------------------------------------------------------------------- */
+int64_t spamd_mttkrp_ws_bytes(int val_dtype, int64_t nnz, int64_t R, int64_t chunk);
+int spamd_mttkrp(int val_dtype, int idx_dtype, int ndim, int mode, int64_t nnz, int64_t R, const void* coords, int64_t ldc,
+                 const void* data, const void* const* factors, const int64_t* pitches, const int64_t* perm,
+                 const int64_t* rowptr, int64_t nrows, int64_t chunk, void* ws, int64_t ws_bytes, void* out, int64_t ldo,
+                 unsigned flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

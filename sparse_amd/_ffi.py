@@ -167,6 +167,9 @@ SIGNATURES = {
     "spamd_cplx_segment_reduce": (_int, [_int, _int, _i64, _vp, _vp, _i64, _i64, _vp, _vp]),
     "spamd_cplx_sum_long_ws_bytes": (_i64, [_i64]),
     "spamd_cplx_sum_long": (_int, [_int, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "spamd_mttkrp_ws_bytes": (_i64, [_int, _i64, _i64, _i64]),
+    "spamd_mttkrp": (_int, [_int, _int, _int, _int, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp,
+                            _i64, _u32, _vp]),
     "spamd_spmm_csr_stream_fits": (_int, [_int, _i64, _i64, _i64, _vp, _vp]),
     "spamd_spmm_csr_stream_passes": (_int, [_int, _i64, _i64, _i64, _vp, _vp, _u32]),
     "spamd_spmm_csr_ldsb_fits": (_int, [_int, _i64, _i64, _i64, _vp, _i64, _vp, _i64]),

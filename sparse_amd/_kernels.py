@@ -1576,6 +1576,79 @@ def sddmm_fold(coords, nlead, a_strides, b_strides, M, N, rows_total, cols_total
 
 
 # ---------------------------------------------------------------------------------------------
+# MTTKRP (csrc/mttkrp.hip)
+# ---------------------------------------------------------------------------------------------
+MTTKRP_MAX_NDIM = 8      # MTTKRP_MAX_NDIM of csrc/mttkrp.hip
+# Elements of a row piece (a sub-group of lanes sums one piece sequentially; longer rows are cut and joined in piece order).
+# A tuning constant of the Python side only: the kernel takes it as an argument.  Chosen with tools/mttkrp_time.py (MI355X,
+# 10^6 stored elements, R = 32, float32, ms per call, median of 5 rounds of 20 calls, spread below 2 %):
+#   chunk                     256     512     1024    2048    4096    8192
+#   ONE row of 10^6           1.341   0.743   0.519   0.549   0.851   1.587     short pieces: the join's chain of piece sums
+#   2000 rows of ~500         0.101   0.111   0.101   0.101   0.101   0.101     (only 256 cuts these rows at all)
+# 1024 is the best of the sweep for the long row and costs the short rows nothing; the first guess, 2048, was 6 % behind.
+MTTKRP_CHUNK = 1024
+
+
+class MttkrpPlan:
+    """The stored elements of a COO grouped by coords[mode]: `rowptr` (int64[shape[mode] + 1]) bounds each row's positions
+    in plan order, `perm` (int64[nnz]) maps a plan position to a stored position - stable, i.e. ascending within a row -
+    or is None when the stored order is the plan order (mode 0 of a canonical COO)."""
+
+    __slots__ = ("mode", "perm", "rowptr")
+
+    def __init__(self, mode, perm, rowptr):
+        self.mode, self.perm, self.rowptr = mode, perm, rowptr
+
+
+def mttkrp_plan(coords, shape, mode):
+    """MttkrpPlan of `coords` ([ndim, nnz], canonical: sorted C-order, no duplicates) for `mode`."""
+    require_hip(coords)
+    nrows = int(shape[mode])
+    if mode == 0:
+        return MttkrpPlan(0, None, rows_to_indptr(coords[0], nrows))
+    keys = coords[mode].to(torch.int64).contiguous()         # (memory plumbing: the sort takes int64 keys)
+    skeys, perm = sort_keys(keys, max(nrows - 1, 0))          # stable: stored order within a row
+    return MttkrpPlan(mode, perm, rows_to_indptr(skeys, nrows))
+
+
+def mttkrp_coo(coords, data, shape, factors, mode, plan, *, chunk=None, exact=False):
+    """out[i, r] = sum_{n: coords[mode][n] == i} data[n] * prod_{d != mode} factors[d][coords[d][n], r]  (spamd_mttkrp):
+    `data` and the used `factors` (2-D device tensors, last axis contiguous) are float32 or all float64, `plan` an
+    MttkrpPlan of the same coordinates and mode.  Returns the dense [shape[mode], R] device tensor."""
+    ndim, nnz = int(coords.shape[0]), int(coords.shape[1])
+    used = [factors[d] for d in range(ndim) if d != mode]
+    dev = require_hip(coords, data, plan.rowptr, plan.perm, *used)
+    dt = data.dtype
+    if dt not in (torch.float32, torch.float64) or any(f.dtype != dt for f in used):
+        raise TypeError("mttkrp: data and factors must all be float32 or all float64")
+    R = int(used[0].shape[1])
+    nrows = int(shape[mode])
+    chunk = MTTKRP_CHUNK if chunk is None else int(chunk)
+    out = torch.empty((nrows, R), dtype=dt, device=dev)
+    coords = coords.contiguous()
+    if not index_dtype_ok(coords):
+        coords = coords.to(torch.int64)
+    keep = []      # factors copied because their last axis is strided: alive until the launch is queued
+    fptr, pitch = [0] * ndim, [0] * ndim
+    for d in range(ndim):
+        if d == mode:
+            continue
+        f = factors[d]
+        if f.shape[1] > 1 and f.stride(1) != 1 or f.shape[0] > 1 and f.stride(0) < R:
+            f = f.contiguous()
+            keep.append(f)
+        fptr[d], pitch[d] = ptr(f), max(int(f.stride(0)), R) if f.shape[0] > 1 else R
+    ws_bytes = int(_ffi.lib().spamd_mttkrp_ws_bytes(code_of(dt), nnz, R, chunk))
+    if ws_bytes < 0:
+        raise _ffi.HipBackendError(f"spamd_mttkrp_ws_bytes failed: {ws_bytes}")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    _ffi.call("spamd_mttkrp", code_of(dt), code_of(coords.dtype), ndim, int(mode), nnz, R, ptr(coords), int(coords.stride(0)) if nnz else 0,
+              ptr(data.contiguous()), (_ct.c_void_p * ndim)(*fptr), _harr64(pitch), ptr(plan.perm), ptr(plan.rowptr), nrows, chunk,
+              ptr(ws), ws_bytes, ptr(out), R, _ffi.EXACT_MULADD if exact else 0, stream_ptr(dev))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # inspector/executor SpMM (csrc/spmm_tiled.hip)
 # ---------------------------------------------------------------------------------------------
 def tiled_params(dtype=torch.float32):

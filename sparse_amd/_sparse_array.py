@@ -75,6 +75,7 @@ class SparseArray:
         out = _copy.copy(self)
         drop_derived(out)
         out.__dict__.pop("_sddmm_plan", None)
+        out.__dict__.pop("_mttkrp_plan", None)
         for name in ("data", "coords", "indices", "indptr", "_keys"):
             t = getattr(self, name, None)
             if isinstance(t, torch.Tensor):
