@@ -753,6 +753,34 @@ int spamd_mttkrp(int val_dtype, int idx_dtype, int ndim, int mode, int64_t nnz, 
                  const int64_t* rowptr, int64_t nrows, int64_t chunk, void* ws, int64_t ws_bytes, void* out, int64_t ldo,
                  unsigned flags, void* stream);
 
+/* =======================================================================================
+ * A13  Masked SpGEMM: sparse x sparse product sampled at a sparse mask (csrc/masked_spgemm.hip) - the reference's
+ *   s * (a @ b) with all three operands sparse (examples/triangles_example.py: sparse.sum(a @ a * a) / 6), without the product:
+ *     out[e] = m[e] * sum over the k stored in both row i of A and column j of B of A[i, k] * B[k, j],  (i, j) = mask position e
+ *   The mask (M x N) and A (M x K) come as CSR - row pointers (M + 1), column indices, values -, B (K x N) as CSC, i.e. the CSR
+ *   arrays of B^T: b_ptr has N + 1 entries, b_idx holds row ids.  Index lists ascend inside a row / column and hold no
+ *   duplicates.  idx_dtype I32 | I64 is the type of all six index arrays, val_dtype F32 | F64 | I32 | I64 the type of the three
+ *   value arrays and of out (nnz values, in the mask's CSR order).  nnz = s_ptr[M].
+ *   Contract (same spirit as spamd_mttkrp): every out element is written exactly once, by one lane; no atomic touches a
+ *   value; results are bitwise reproducible and depend neither on the launch geometry nor on group / cap / window.
+ *     acc = +0;  for every common k, ascending:  acc = acc + A[i, k] * B[k, j];   out = m * acc
+ *   flags: SPAMD_EXACT_MULADD rounds every multiply and add on its own; without it the multiply and add of a term are one
+ *   fma.  The mask multiply is always its own operation.  Integers wrap.  A position without a common k gets +0 (all-zero
+ *   bits) whatever m is - also for a NaN or infinite m -, so the prune of the result removes it.
+ *   group: lanes that walk one column of B together, 8 | 16 | 32 | 64.  cap: a row of A of at most cap entries (1 .. 2048) is
+ *   searched in LDS, a longer one in global memory.  window: mask elements per wave (>= 1; values above nnz mean nnz); rows
+ *   are cut at window bounds.  The arrays are trusted, as by every product entry point: pointers ascend from 0, s_idx < N,
+ *   a_idx and b_idx < K (K itself is only checked for its sign: no array is sized by it).
+ *   zeros (device uint64, may be NULL): receives the number of out values whose bits are all zero (one integer add per wave;
+ *   zeroed by the call).
+ *   Returns before any launch: SPAMD_ETYPE for other type codes, SPAMD_EINVAL for negative sizes or group / cap / window
+ *   outside the above, 0 for nnz == 0, M == 0 or N == 0.  No workspace.
+ * ------------------------------------------------------------------------------------- */
+int spamd_masked_spgemm(int val_dtype, int idx_dtype, int64_t M, int64_t N, int64_t K, int64_t nnz, const void* s_ptr,
+                        const void* s_idx, const void* s_val, const void* a_ptr, const void* a_idx, const void* a_val,
+                        const void* b_ptr, const void* b_idx, const void* b_val, int group, int cap, int64_t window, void* out,
+                        void* zeros, unsigned flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,6 +36,7 @@ from ._batched import concatenate, stack
 from ._broadcast import broadcast_to
 from ._io import load_npz, save_npz
 from ._mttkrp import mttkrp
+from ._masked import masked_matmul
 from ._api import (all, any, argwhere, asarray, astype, empty, empty_like, expand_dims, eye, full, full_like,
                    matrix_transpose, max, mean, min, moveaxis, nanmax, nanmean, nanmin, nanprod, nanreduce, nansum, nonzero,
                    ones, ones_like, permute_dims, prod, random, reshape, sddmm, squeeze, std, sum, var, vecdot, where, zeros,
@@ -55,7 +56,7 @@ __all__ = ["COO", "GCXS", "SparseArray", "HipBackendError", "abs", "acos", "acos
            "cos", "cosh", "diagonal", "diagonalize", "divide", "e", "equal", "exp", "expm1", "finfo", "flip", "float16",
            "float32", "float64", "floor", "floor_divide", "greater", "greater_equal", "hypot", "iinfo", "imag", "inf", "int16",
            "int32", "int64", "int8", "isdtype", "isfinite", "isinf", "isnan", "isneginf", "isposinf", "kron", "less", "less_equal",
-           "log", "log10", "log1p", "log2", "logaddexp", "logical_and", "logical_not", "logical_or", "logical_xor", "maximum",
+           "log", "log10", "log1p", "log2", "logaddexp", "logical_and", "logical_not", "logical_or", "logical_xor", "masked_matmul", "maximum",
            "minimum", "mttkrp", "multiply", "nan", "negative", "newaxis", "nextafter", "not_equal", "outer", "pad", "pi", "positive", "pow",
            "real", "reciprocal", "remainder", "result_type", "roll", "round", "sign", "signbit", "sin", "sinh", "sqrt",
            "square", "subtract", "tan", "tanh", "sort", "tril", "triu", "trunc", "uint16", "uint32", "uint64", "uint8", 

@@ -170,6 +170,8 @@ SIGNATURES = {
     "spamd_mttkrp_ws_bytes": (_i64, [_int, _i64, _i64, _i64]),
     "spamd_mttkrp": (_int, [_int, _int, _int, _int, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp,
                             _i64, _u32, _vp]),
+    "spamd_masked_spgemm": (_int, [_int, _int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _i64,
+                                   _vp, _vp, _u32, _vp]),
     "spamd_spmm_csr_stream_fits": (_int, [_int, _i64, _i64, _i64, _vp, _vp]),
     "spamd_spmm_csr_stream_passes": (_int, [_int, _i64, _i64, _i64, _vp, _vp, _u32]),
     "spamd_spmm_csr_ldsb_fits": (_int, [_int, _i64, _i64, _i64, _vp, _i64, _vp, _i64]),

@@ -1649,6 +1649,62 @@ def mttkrp_coo(coords, data, shape, factors, mode, plan, *, chunk=None, exact=Fa
 
 
 # ---------------------------------------------------------------------------------------------
+# masked SpGEMM (csrc/masked_spgemm.hip)
+# ---------------------------------------------------------------------------------------------
+MASKED_DTYPES = (torch.float32, torch.float64, torch.int32, torch.int64)
+MASKED_GROUPS = (8, 16, 32, 64)
+MASKED_MAX_CAP = 2048        # MSG_MAX_CAP of csrc/masked_spgemm.hip
+# Tuning constants of the Python side only (the kernel takes them as arguments; none of them changes a bit of the result):
+# MASKED_GROUP lanes walk one column of B together, a row of A of at most MASKED_CAP entries is searched in LDS (4 waves x
+# cap x 4 or 8 bytes per workgroup), a wave owns MASKED_WINDOW consecutive mask elements.  Chosen with
+# tools/masked_matmul_time.py --sweep (MI355X, symmetric graph of 2^17 nodes, mean degree 32, s = a = b, float32, 32-bit
+# indices, ms per kernel call, median of 5 rounds of 20 calls, spread below 1 %), one parameter at a time around 16 / 256 / 256:
+#   group    8: 0.687   16: 0.739   32: 0.906   64: 1.152
+#   cap      1: 1.461   64 .. 512: 0.739   1024: 0.978   2048: 1.767      (1 = every search in global memory)
+#   window  64: 0.921  128: 0.730  256: 0.739   512: 0.897  1024: 0.939  4096: 3.165
+# and jointly group 8 | 16 x cap 64 | 128 | 256 x window 256 | 1024: cap makes no difference below 1024, window 1024 costs
+# 26-27 %, group 8 is 7 % ahead of 16 on this graph (columns of ~32 entries); 16 is kept for longer columns (DESIGN A13, open).
+MASKED_GROUP = 16
+MASKED_CAP = 256
+MASKED_WINDOW = 256
+
+
+def masked_spgemm(shape, s_csr, a_csr, b_csc, *, group=None, cap=None, window=None, exact=False):
+    """out[e] = m[e] * sum over common k of A[i, k] * B[k, j] at every stored position e = (i, j) of the mask, in the mask's
+    CSR order (spamd_masked_spgemm; the order contract is in include/sparse_amd.h, A13).  `shape` = (M, N, K); `s_csr`,
+    `a_csr`: (data, indices, indptr) compressed by rows, `b_csc`: the same compressed by columns (the CSR triplet of B^T);
+    the three value arrays have one of MASKED_DTYPES.  Returns the values; the number of all-zero-bit results is left on
+    them (`note_zero_bits_count`)."""
+    M, N, Kd = (int(v) for v in shape)
+    (s_val, s_idx, s_ptr), (a_val, a_idx, a_ptr), (b_val, b_idx, b_ptr) = s_csr, a_csr, b_csc
+    dev = require_hip(s_val, s_idx, s_ptr, a_val, a_idx, a_ptr, b_val, b_idx, b_ptr)
+    dt = s_val.dtype
+    if dt not in MASKED_DTYPES or a_val.dtype != dt or b_val.dtype != dt:
+        raise TypeError("masked_spgemm: the three value arrays must share one of float32, float64, int32, int64")
+    group = MASKED_GROUP if group is None else int(group)
+    cap = MASKED_CAP if cap is None else int(cap)
+    window = MASKED_WINDOW if window is None else int(window)
+    if group not in MASKED_GROUPS:
+        raise ValueError(f"group must be one of {MASKED_GROUPS}, got {group}")
+    if not 1 <= cap <= MASKED_MAX_CAP:
+        raise ValueError(f"cap must be in 1 .. {MASKED_MAX_CAP}, got {cap}")
+    if window < 1:
+        raise ValueError(f"window must be positive, got {window}")
+    if s_ptr.numel() != M + 1 or a_ptr.numel() != M + 1 or b_ptr.numel() != N + 1:
+        raise ValueError("masked_spgemm: pointer arrays do not match the shapes")
+    idx, it = _unify_index(*[t.contiguous() for t in (s_ptr, s_idx, a_ptr, a_idx, b_ptr, b_idx)])
+    s_ptr, s_idx, a_ptr, a_idx, b_ptr, b_idx = idx
+    nnz = int(s_idx.numel())
+    out = torch.empty(nnz, dtype=dt, device=dev)
+    zeros = torch.empty(1, dtype=torch.int64, device=dev)
+    _ffi.call("spamd_masked_spgemm", code_of(dt), code_of(it), M, N, Kd, nnz, ptr(s_ptr), ptr(s_idx), ptr(s_val.contiguous()),
+              ptr(a_ptr), ptr(a_idx), ptr(a_val.contiguous()), ptr(b_ptr), ptr(b_idx), ptr(b_val.contiguous()), group, cap, window,
+              ptr(out), ptr(zeros), _ffi.EXACT_MULADD if exact else 0, stream_ptr(dev))
+    note_zero_bits_count(out, zeros)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # inspector/executor SpMM (csrc/spmm_tiled.hip)
 # ---------------------------------------------------------------------------------------------
 def tiled_params(dtype=torch.float32):
