@@ -19,6 +19,7 @@
 #include <string.h>
 #include <cstring>
 #include "common.h"
+#include "group_of.h"  // GroupOf / GroupOfD: the group id of a key, k / divisor
 #include <rocprim/rocprim.hpp>
 
 namespace spamd {
@@ -27,35 +28,6 @@ constexpr int GR_THREADS = 512;
 constexpr int GR_ITEMS = 4;  // 32 bytes of keys per lane, two 16-byte loads (8 items per thread was no faster, 2 items
                              // doubles the segmented-scan work per element)
 constexpr int GR_TILE = GR_THREADS * GR_ITEMS;
-
-// k / d for 0 <= k: reciprocal multiply in double, then an exact integer correction (a hardware 64-bit divide
-// is ~100 instructions)
-struct GroupOf {
-  int64_t d;
-  double rd;
-  __device__ __forceinline__ int64_t operator()(int64_t k) const {
-    int64_t q = (int64_t)((double)k * rd);
-    int64_t r = k - q * d;
-    while (r < 0) { --q; r += d; }
-    while (r >= d) { ++q; r -= d; }
-    return q;
-  }
-};
-
-// The same for keys below 2^53 (every array with fewer than 2^53 elements), entirely in double precision: k, the
-// quotient and the remainder k - q*d are all exactly representable, so one fma decides the +-1 correction and no
-// 64-bit integer multiply or conversion back is needed.  Group ids are compared (and stored) as doubles.
-struct GroupOfD {
-  double d, rd;
-  __device__ __forceinline__ double operator()(int64_t k) const {
-    const double kd = (double)k;
-    double q = __builtin_floor(kd * rd);
-    const double r = __builtin_fma(-q, d, kd);
-    if (r < 0.0) q -= 1.0;
-    if (r >= d) q += 1.0;
-    return q;
-  }
-};
 
 enum { GR_ADD = 0, GR_MUL, GR_MAX, GR_MIN, GR_OR, GR_AND, GR_FMAX, GR_FMIN };
 

@@ -130,7 +130,13 @@ def test_broadcasting_and_npz_interchange(sp, tmp_path):
 @pytest.mark.parametrize("dtype", [np.int64, np.float64, np.float32])
 def test_reductions_with_runs_longer_than_a_tile(dtype):
     """Grouped reduce (csrc/group_reduce.hip): runs that span many 2048-element tiles (full reduction, one long
-    group among short ones) go through the chained fix-up; checked against NumPy on the dense array."""
+    group among short ones) go through the chained fix-up; checked against NumPy on the dense array.  Integers, max and
+    min are exact (sums and products wrap; the factors are odd, so a product of stored values is never 0).  Float sums:
+    every output element against math.fsum of its slice, within Higham's bound for m stored terms added in any order in
+    the value type, gamma_(m-1) * sum|v| + u |exact| (tests/reduce_cases.py)."""
+    import math
+
+    import reduce_cases as RC
     import sparse_amd as sp
 
     rng = np.random.default_rng(5)
@@ -138,18 +144,32 @@ def test_reductions_with_runs_longer_than_a_tile(dtype):
     dense = np.zeros(shape, dtype=dtype)
     mask = rng.random(shape) < 0.15
     mask[2] = True  # one group of 630000 elements when reducing over the last two axes
-    vals = rng.integers(-40, 40, size=int(mask.sum())) if np.dtype(dtype).kind == "i" else rng.random(int(mask.sum())) - 0.4
+    integer = np.dtype(dtype).kind == "i"
+    vals = rng.integers(-40, 40, size=int(mask.sum())) | 1 if integer else rng.random(int(mask.sum())) - 0.4
     dense[mask] = vals.astype(dtype)
+    assert np.count_nonzero(dense) == int(mask.sum())
     x = sp.COO.from_numpy(dense)
     for axis in (None, (1, 2), 2, (0, 1)):
-        for name in ("sum", "max", "min"):
+        for name in ("sum", "max", "min") + (("prod",) if integer else ()):
             got = getattr(x, name)(axis=axis)
             want = getattr(dense, name)(axis=axis)
             got = got.todense() if hasattr(got, "todense") else np.asarray(got)
-            if np.dtype(dtype).kind == "i" or name != "sum":
+            if integer or name != "sum":
                 assert np.array_equal(got, want), (name, axis)
-            else:
-                assert np.allclose(got, want, rtol=1e-5 if dtype == np.float32 else 1e-12), (name, axis)
+                continue
+            red = tuple(range(3)) if axis is None else (axis if isinstance(axis, tuple) else (axis,))
+            kept = tuple(a for a in range(3) if a not in red)
+            rows = dense.transpose(kept + red).reshape(int(np.prod([shape[a] for a in kept], dtype=np.int64)), -1).astype(np.float64)
+            stored = mask.transpose(kept + red).reshape(rows.shape).sum(axis=1)
+            assert got.size == len(rows)
+            worst = 0.0
+            for r, (row, m, g) in enumerate(zip(rows, stored.tolist(), np.asarray(got, dtype=np.float64).reshape(-1).tolist())):
+                row = row.tolist()
+                exact = math.fsum(row)
+                bound = RC.sum_bound(m, math.fsum(map(abs, row)), exact, dtype)
+                worst = max(worst, abs(g - exact) / bound if bound else float(g != exact))
+                assert abs(g - exact) <= bound, (name, axis, r, m, g, exact, bound)
+            print(f"sum axis={axis} {np.dtype(dtype).name}: largest error / bound = {worst:.3f}")
 
 
 @pytest.mark.gpu
