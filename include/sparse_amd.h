@@ -781,6 +781,45 @@ int spamd_masked_spgemm(int val_dtype, int idx_dtype, int64_t M, int64_t N, int6
                         const void* b_ptr, const void* b_idx, const void* b_val, int group, int cap, int64_t window, void* out,
                         void* zeros, unsigned flags, void* stream);
 
+/* =======================================================================================
+ * A14  softmax over the stored elements of a sparse array (csrc/softmax.hip, csrc/exp_det.h): unstored positions count as
+ *   minus infinity, so the result has the stored structure of the input - the step between the scores of spamd_sddmm and the
+ *   product that follows.  The reference has no softmax; the meaning is scipy.special.softmax of the dense array with -inf
+ *   at the unstored positions, read back at the stored ones.
+ *   The stored elements come grouped: segptr (idx_dtype I32 | I64, nseg + 1 entries ascending from 0 to nnz) bounds group
+ *   g's positions in plan order; perm (int64[nnz], may be NULL = the stored order) maps a plan position to a stored
+ *   position.  x and out (val_dtype F32 | F64, nnz values, out != x) are indexed by stored position.  An empty group writes
+ *   nothing.  has_scale != 0: t_i = (T)scale * x_i, one multiply in the value type, before anything else; else t_i = x_i.
+ *   Contract: every out element is written exactly once; no atomic touches a value; results are bitwise reproducible and
+ *   depend neither on the launch geometry nor on group / short_max / max_len.  For one group t_0 .. t_{n-1} in plan order:
+ *     m    = the maximum of the t_i.  Exact; any NaN makes it NaN; known before any exponential is taken (no online
+ *            rescaling of partial sums); the sign of a zero maximum changes no result
+ *     d_i  = t_i - m
+ *     e_i  = exp_det(d_i): csrc/exp_det.h - k = rint(d * log2 e), two-constant Cody-Waite reduction in fmas, a Taylor
+ *            polynomial in Horner fmas, ldexp; exp_det(+-0) = 1, exp_det(d) = +0 below the underflow threshold (-inf
+ *            included), NaN for NaN.  Not the device math library's exp: every step is one exactly rounded IEEE operation
+ *     s    = the group is cut into pieces of `chunk` elements.  A piece is summed by 64 accumulators - accumulator l adds
+ *            the piece's elements l, l + 64, l + 128, .. in order - folded by halving: a[l] = a[l] + a[l + h] for h = 32,
+ *            16, 8, 4, 2, 1.  The piece sums are added in piece order.  A group of at most `chunk` elements is one piece,
+ *            so `chunk` enters the order of longer groups only
+ *     p_i  = e_i / s, one correctly rounded division
+ *   Hence: a group that holds a NaN or +inf, or only -inf, is NaN throughout; -inf beside finite values gives +0.0.
+ *   group: lanes that own one short group, 8 | 16 | 32 | 64.  short_max (0 .. 64): groups of at most short_max elements take
+ *   the sub-group form, longer ones up to `chunk` a wave each, longer ones pieces (five launches, each of which ends before
+ *   the next reads its results: no workgroup waits for another).  chunk: a multiple of 64 in 64 .. 1024.  max_len: the
+ *   length of the longest group, 0 .. nnz (the caller knows it from building segptr); it only decides which launches are
+ *   made - a group longer than max_len may be left unwritten, nothing is read or written out of bounds for it.
+ *   ws: spamd_softmax_ws_bytes(val_dtype, nnz, chunk) bytes (0 when nnz <= chunk), needed when max_len > chunk (SPAMD_EWS).
+ *   The arrays are trusted, as by every entry point: segptr ascends from 0 to nnz, perm holds positions below nnz.
+ *   Returns before any launch: SPAMD_ETYPE for other type codes; SPAMD_EINVAL for negative sizes, max_len > nnz, group /
+ *   short_max / chunk outside the above, null pointers with work to do or out == x; 0 for nseg == 0, nnz == 0 or
+ *   max_len == 0.
+ * ------------------------------------------------------------------------------------- */
+int64_t spamd_softmax_ws_bytes(int val_dtype, int64_t nnz, int64_t chunk);
+int spamd_softmax(int val_dtype, int idx_dtype, int64_t nseg, int64_t nnz, const void* segptr, const int64_t* perm,
+                  const void* x, int has_scale, double scale, int group, int64_t short_max, int64_t chunk, int64_t max_len,
+                  void* ws, int64_t ws_bytes, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

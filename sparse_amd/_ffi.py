@@ -172,6 +172,9 @@ SIGNATURES = {
                             _i64, _u32, _vp]),
     "spamd_masked_spgemm": (_int, [_int, _int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _i64,
                                    _vp, _vp, _u32, _vp]),
+    "spamd_softmax_ws_bytes": (_i64, [_int, _i64, _i64]),
+    "spamd_softmax": (_int, [_int, _int, _i64, _i64, _vp, _vp, _vp, _int, _C.c_double, _int, _i64, _i64, _i64, _vp, _i64, _vp,
+                             _vp]),
     "spamd_spmm_csr_stream_fits": (_int, [_int, _i64, _i64, _i64, _vp, _vp]),
     "spamd_spmm_csr_stream_passes": (_int, [_int, _i64, _i64, _i64, _vp, _vp, _u32]),
     "spamd_spmm_csr_ldsb_fits": (_int, [_int, _i64, _i64, _i64, _vp, _i64, _vp, _i64]),

@@ -1649,6 +1649,67 @@ def mttkrp_coo(coords, data, shape, factors, mode, plan, *, chunk=None, exact=Fa
 
 
 # ---------------------------------------------------------------------------------------------
+# softmax over stored elements (csrc/softmax.hip)
+# ---------------------------------------------------------------------------------------------
+SOFTMAX_GROUPS = (8, 16, 32, 64)
+SOFTMAX_MAX_CHUNK = 1024     # SOFTMAX_MAX_CHUNK of csrc/softmax.hip: a wave holds a group of that many elements in registers
+SOFTMAX_FORMS = ("short", "wide", "long")
+# SOFTMAX_CHUNK is part of the order contract for groups longer than it (pieces of that many elements, include/sparse_amd.h
+# A14) and of no shorter group; SOFTMAX_SHORT_MAX (groups of at most that many elements go to a sub-group of lanes, longer
+# ones to a whole wave) and SOFTMAX_GROUP (the sub-group's width) never change a bit.  Chosen with tools/softmax_time.py
+# --sweep (MI355X, float32, ms per kernel call through this wrapper, median of 5 rounds of 20 calls, spread below 2 %), one
+# parameter at a time: (a) CSR graph of 2^17 nodes, mean degree 32; (b) one hub row of 10^6 among 2^16 rows of 8; (c) COO
+# batch 16 x 2048 x 2048, 32 per row:
+#   group          8       16      32      64
+#     (a)        0.0127  0.0143  0.0196  0.0303     fewer lanes per group = more values per lane and fewer shuffle steps
+#     (b)        0.0964  0.0972  0.0998  0.1045
+#     (c)        0.0084  0.0082  0.0083  0.0087
+#   short_max      0       16      32      64       (0 = every group a whole wave)
+#     (a)        0.0985  0.1077  0.0816  0.0192
+#     (c)        0.0907  0.0938  0.0590  0.0087
+#   chunk          64      128     256     512     1024
+#     (b)        0.926   0.478   0.252   0.147   0.0997    short pieces: more windows to search, longer chains of piece sums
+SOFTMAX_CHUNK = 1024
+SOFTMAX_SHORT_MAX = 64
+SOFTMAX_GROUP = 8
+
+
+def softmax_segments(segptr, perm, data, max_len, *, scale=None, group=None, chunk=None, form=None, short_max=None):
+    """softmax of every segment of `data` (spamd_softmax): `segptr` (int32 | int64 [nseg + 1], ascending from 0 to nnz) bounds
+    the groups' positions in plan order, `perm` (int64[nnz] or None) maps a plan position to a stored position, `data` is
+    float32 or float64, `max_len` the longest group's length.  Returns a new tensor in the stored order of `data`.
+    `scale`: None or a real scalar (rounded to the data type once).  `form` forces a kernel form, for tests and sweeps:
+    "short" (sub-groups of `group` lanes; every group has at most 64 elements), "wide" (a wave per group; at most `chunk`
+    elements), "long" (a wave per group up to `chunk`, default 64 here, pieces beyond); `short_max` moves the length at which
+    the default hands a group from a sub-group to a wave (sweeps)."""
+    dev = require_hip(segptr, perm, data)
+    dt = data.dtype
+    if dt not in (torch.float32, torch.float64):
+        raise TypeError("softmax: data must be float32 or float64")
+    if not index_dtype_ok(segptr) or (perm is not None and perm.dtype != torch.int64):
+        raise TypeError("softmax: segptr must be int32 or int64 and perm int64")
+    nnz, nseg, max_len = int(data.numel()), int(segptr.numel()) - 1, int(max_len)
+    if form not in (None,) + SOFTMAX_FORMS:
+        raise ValueError(f"softmax: form must be one of {SOFTMAX_FORMS} or None, got {form!r}")
+    chunk = (64 if form == "long" else SOFTMAX_CHUNK) if chunk is None else int(chunk)
+    short_max = (SOFTMAX_SHORT_MAX if short_max is None else int(short_max)) if form in (None, "short") else 0
+    if form == "short" and max_len > 64 or form == "wide" and max_len > chunk:
+        raise ValueError(f"softmax: form {form!r} does not take a group of {max_len} elements")
+    group = SOFTMAX_GROUP if group is None else int(group)
+    out = torch.empty_like(data, memory_format=torch.contiguous_format)
+    ws_bytes = int(_ffi.lib().spamd_softmax_ws_bytes(code_of(dt), nnz, chunk)) if max_len > chunk else 0
+    if ws_bytes < 0:
+        raise _ffi.HipBackendError(f"spamd_softmax_ws_bytes failed: {ws_bytes}")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    has_scale = scale is not None
+    sc = float(np.asarray(scale).astype(np_dtype(dt))) if has_scale else 0.0
+    _ffi.call("spamd_softmax", code_of(dt), code_of(segptr.dtype), nseg, nnz, ptr(segptr.contiguous()), ptr(perm),
+              ptr(data.contiguous()), int(has_scale), sc, group, short_max, chunk, max_len, ptr(ws), ws_bytes, ptr(out),
+              stream_ptr(dev))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # masked SpGEMM (csrc/masked_spgemm.hip)
 # ---------------------------------------------------------------------------------------------
 MASKED_DTYPES = (torch.float32, torch.float64, torch.int32, torch.int64)
