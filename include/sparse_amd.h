@@ -820,6 +820,47 @@ int spamd_softmax(int val_dtype, int idx_dtype, int64_t nseg, int64_t nnz, const
                   const void* x, int has_scale, double scale, int group, int64_t short_max, int64_t chunk, int64_t max_len,
                   void* ws, int64_t ws_bytes, void* out, void* stream);
 
+/* =======================================================================================
+ * A15  sparse attention (csrc/attention.hip): for every head h,
+ *     out[h] = softmax_over_stored(scale * (s (.) (q[h] k[h]^T))) @ v[h]
+ *   over the stored positions of ONE 2-D mask s (M x N) - the scores of spamd_sddmm, the softmax of A14 and the product by v
+ *   fused, the scores never written for rows of at most `chunk` elements.  An unstored position counts as minus infinity; a
+ *   stored zero of s, or a score that comes out 0, takes part as the value 0; a row without stored elements gives +0.0.
+ *   The mask comes as CSR: s_ptr (idx_dtype I32 | I64, M + 1 entries ascending from 0 to nnz), s_idx (column ids, same type),
+ *   s_val (val_dtype F32 | F64).  "Stored order" below is the order of these arrays.  q (H, M, D), k (H, N, D), v (H, N, Dv)
+ *   are dense arrays of val_dtype whose last axis is contiguous: row r of head h of q starts at q + h * q_head + r * q_pitch
+ *   (elements), likewise k and v.  out is (H, M, Dv), contiguous, of val_dtype.
+ *   Contract: every operation is rounded once (an fma counts as one; there is no EXACT variant, as in A14); every out element
+ *   is written exactly once; no atomic touches a value; results are bitwise reproducible and depend neither on the launch
+ *   geometry nor on group / short_max / max_len.  For row r of one head, stored elements i = 0 .. n-1, columns c_i:
+ *     w_i   = dot(q[r], k[c_i]) by 64 accumulators: accumulator l starts at +0.0 and takes a_l = fma(q[r][l + 64 j],
+ *             k[c_i][l + 64 j], a_l) for j ascending (an element past D contributes nothing), then the accumulators are folded
+ *             by halving, a[l] = a[l] + a[l + h] for h = 32, 16, 8, 4, 2, 1 - the tree A14 uses for its sums
+ *     t_i   = s_i * w_i, one multiply; has_scale != 0: t_i = (T)scale * t_i, one more
+ *     p_i   = exactly A14's result for the group t_0 .. t_{n-1} without a further scale, at the same `chunk`: the maximum
+ *             before any exponential, exp_det, 64 accumulators per piece of `chunk`, one correctly rounded division
+ *     out[r][j]: the elements are cut into pieces of `chunk`; a piece starts at +0.0 and takes acc = fma(p_i, v[c_i][j], acc)
+ *             for i ascending; the piece sums are added in piece order, the first piece's sum being the start.  A row of at
+ *             most `chunk` elements is one piece, so `chunk` enters the order of longer rows only
+ *   Hence: a row whose scores hold a NaN or +inf, or only -inf, is NaN throughout its output row.
+ *   group: lanes that own one short (row, head), 8 | 16 | 32 | 64.  short_max (0 .. 64): rows of at most short_max elements
+ *   take the sub-group form, longer ones up to `chunk` a wave each (scores in LDS), longer ones pieces through the workspace
+ *   (six launches, each of which ends before the next reads its results: no workgroup waits for another).  chunk: a multiple
+ *   of 64 in 64 .. 1024.  max_len: the length of the longest row, 0 .. nnz; it only decides which launches are made.
+ *   ws: spamd_attention_ws_bytes(val_dtype, nnz, H, Dv, chunk) bytes (0 when nnz <= chunk), needed when max_len > chunk
+ *   (SPAMD_EWS).  The arrays are trusted, as by every entry point: s_ptr ascends from 0 to nnz, s_idx < N (N itself is only
+ *   checked for its sign).
+ *   Returns before any launch: SPAMD_ETYPE for other type codes; SPAMD_EINVAL for negative sizes, pitches or strides,
+ *   max_len > nnz, group / short_max / chunk outside the above, or null pointers with work to do; 0 for M == 0, H == 0 or
+ *   Dv == 0.  nnz == 0 writes +0.0 everywhere.
+ * ------------------------------------------------------------------------------------- */
+int64_t spamd_attention_ws_bytes(int val_dtype, int64_t nnz, int64_t H, int64_t Dv, int64_t chunk);
+int spamd_attention(int val_dtype, int idx_dtype, int64_t M, int64_t N, int64_t nnz, int64_t H, int64_t D, int64_t Dv,
+                    const void* s_ptr, const void* s_idx, const void* s_val, const void* q, int64_t q_pitch, int64_t q_head,
+                    const void* k, int64_t k_pitch, int64_t k_head, const void* v, int64_t v_pitch, int64_t v_head,
+                    int has_scale, double scale, int group, int64_t short_max, int64_t chunk, int64_t max_len, void* ws,
+                    int64_t ws_bytes, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1710,6 +1710,90 @@ def softmax_segments(segptr, perm, data, max_len, *, scale=None, group=None, chu
 
 
 # ---------------------------------------------------------------------------------------------
+# sparse attention (csrc/attention.hip)
+# ---------------------------------------------------------------------------------------------
+ATTENTION_GROUPS = SOFTMAX_GROUPS
+ATTENTION_FORMS = SOFTMAX_FORMS
+# ATTENTION_CHUNK is part of the order contract for rows longer than it (include/sparse_amd.h A15: the pieces of the softmax
+# sum and of the output) and of no shorter row: a multiple of 64, at most SOFTMAX_MAX_CHUNK.  ATTENTION_SHORT_MAX and
+# ATTENTION_GROUP never change a bit.  Chosen with tools/attention_time.py --sweep (MI355X, float32, ms per kernel call through
+# this wrapper, median of 5 rounds of 20 calls, spread below 1 %), one parameter at a time: (a) CSR graph of 2^17 nodes, mean
+# degree 32, D = Dv = 64; (b) the same graph, 8 heads of D = Dv = 16; (c) one hub row of 10^6 among 2^16 rows of 8, D = Dv = 64:
+#   group          8       16      32      64
+#     (a)        0.300   0.284   0.305   0.514      16: four accumulators a lane at D = 64, four shuffle steps, four waves a SIMD
+#     (b)        1.888   1.538   2.205   3.992
+#   short_max      0       16      32      64       (0 = every row a whole wave)
+#     (a)        1.351   1.358   1.036   0.284
+#     (b)        4.693   4.716   3.775   1.539
+#   chunk          64      128     256     512     1024
+#     (c)        7.90    4.07    2.25    1.48    1.28
+ATTENTION_CHUNK = SOFTMAX_CHUNK
+ATTENTION_SHORT_MAX = 64
+ATTENTION_GROUP = 16
+
+
+def _rows3(t, dev):
+    """(tensor [H, rows, width] whose last axis is contiguous, row pitch, head stride) of a dense operand [..., rows, width]: a
+    view where the strides allow it, else one copy (a strided last axis, rows that overlap, leading axes that do not fold)"""
+    rows, width = int(t.shape[-2]), int(t.shape[-1])
+    H = 1
+    for n in t.shape[:-2]:
+        H *= int(n)
+    if width > 1 and t.stride(-1) != 1 or rows > 1 and t.stride(-2) < width:
+        t = t.contiguous()
+    t3 = t.reshape(H, rows, width)             # (a view when the leading axes fold into one stride, else the one copy)
+    if width > 1 and t3.stride(2) != 1 or rows > 1 and t3.stride(1) < width or H > 1 and t3.stride(0) < 0:
+        t3 = t3.contiguous()
+    pitch = int(t3.stride(1)) if rows > 1 else width
+    head = int(t3.stride(0)) if H > 1 else 0
+    return t3, pitch, head
+
+
+def attention_rows(indptr, indices, svals, q, k, v, max_len, *, scale=None, group=None, chunk=None, form=None, short_max=None):
+    """out[h] = softmax_over_stored(scale * (s * (q[h] @ k[h].T))) @ v[h] for the CSR mask (`svals`, `indices`, `indptr`: M + 1
+    int32 | int64 pointers) (spamd_attention).  `q` [..., M, D], `k` [..., N, D], `v` [..., N, Dv] are device tensors of the
+    type of `svals` (float32 or float64) with the same leading axes; `max_len` is the longest row's length.  Returns the
+    dense [..., M, Dv] tensor.  `form` forces a kernel form, for tests and sweeps: "short" (sub-groups of `group` lanes; every
+    row has at most 64 elements), "wide" (a wave per row; at most `chunk` elements), "long" (a wave per row up to `chunk`,
+    default 64 here, pieces beyond); `short_max` moves the length at which a row goes from a sub-group to a wave (sweeps)."""
+    dev = require_hip(indptr, indices, svals, q, k, v)
+    dt = svals.dtype
+    if dt not in (torch.float32, torch.float64) or any(t.dtype != dt for t in (q, k, v)):
+        raise TypeError("attention: the mask values, q, k and v must all be float32 or all float64")
+    if not index_dtype_ok(indptr) or indices.dtype != indptr.dtype:
+        raise TypeError("attention: indptr and indices must both be int32 or both int64")
+    lead = tuple(q.shape[:-2])
+    if tuple(k.shape[:-2]) != lead or tuple(v.shape[:-2]) != lead:
+        raise ValueError("attention: q, k and v must have the same leading axes")
+    M, D, N, Dv = int(q.shape[-2]), int(q.shape[-1]), int(k.shape[-2]), int(v.shape[-1])
+    if int(k.shape[-1]) != D or int(v.shape[-2]) != N or int(indptr.numel()) != M + 1:
+        raise ValueError("attention: shape mismatch between the mask, q, k and v")
+    nnz, max_len = int(svals.numel()), int(max_len)
+    if form not in (None,) + ATTENTION_FORMS:
+        raise ValueError(f"attention: form must be one of {ATTENTION_FORMS} or None, got {form!r}")
+    chunk = (64 if form == "long" else ATTENTION_CHUNK) if chunk is None else int(chunk)
+    short_max = (ATTENTION_SHORT_MAX if short_max is None else int(short_max)) if form in (None, "short") else 0
+    if form == "short" and max_len > 64 or form == "wide" and max_len > chunk:
+        raise ValueError(f"attention: form {form!r} does not take a row of {max_len} elements")
+    group = ATTENTION_GROUP if group is None else int(group)
+    q3, qp, qh = _rows3(q, dev)
+    k3, kp, kh = _rows3(k, dev)
+    v3, vp, vh = _rows3(v, dev)
+    H = int(q3.shape[0])
+    out = torch.empty(lead + (M, Dv), dtype=dt, device=dev)
+    ws_bytes = int(_ffi.lib().spamd_attention_ws_bytes(code_of(dt), nnz, H, Dv, chunk)) if max_len > chunk else 0
+    if ws_bytes < 0:
+        raise _ffi.HipBackendError(f"spamd_attention_ws_bytes failed: {ws_bytes}")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    has_scale = scale is not None
+    sc = float(np.asarray(scale).astype(np_dtype(dt))) if has_scale else 0.0
+    _ffi.call("spamd_attention", code_of(dt), code_of(indptr.dtype), M, N, nnz, H, D, Dv, ptr(indptr.contiguous()),
+              ptr(indices.contiguous()), ptr(svals.contiguous()), ptr(q3), qp, qh, ptr(k3), kp, kh, ptr(v3), vp, vh,
+              int(has_scale), sc, group, short_max, chunk, max_len, ptr(ws), ws_bytes, ptr(out), stream_ptr(dev))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # masked SpGEMM (csrc/masked_spgemm.hip)
 # ---------------------------------------------------------------------------------------------
 MASKED_DTYPES = (torch.float32, torch.float64, torch.int32, torch.int64)

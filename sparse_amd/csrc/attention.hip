@@ -1,0 +1,633 @@
+// A15  sparse attention: for every head, out = softmax_over_stored(scale * (s (.) (q k^T))) @ v over the stored positions of a
+// 2-D mask s (M x N, CSR: ptr, idx, sv), fused - the SDDMM scores, the softmax of A14 and the SpMM by v in one pass over the
+// mask, the scores never written (rows of at most `chunk` elements).  q (H, M, D), k (H, N, D), v (H, N, Dv) are dense with
+// a row pitch and a head stride each (last axis contiguous); out is (H, M, Dv), contiguous.  Every head reads the same mask.
+//
+// Order (the contract tests/attention_cases.py restates, bit for bit; include/sparse_amd.h A15), for row r of one head with
+// stored elements i = 0 .. n-1 in stored order and columns c_i:
+//   w_i  = dot(q[r], k[c_i]) by 64 accumulators: accumulator l starts at +0.0 and takes a_l = fma(q[l + 64 j], k[c_i][l + 64 j],
+//          a_l) for j ascending (an element past D contributes nothing); folded by halving, a[l] = a[l] + a[l + h], h = 32 .. 1
+//   t_i  = s_i * w_i (one multiply);  t_i = scale * t_i (one more) when a scale is given
+//   p_i  = A14's softmax of t_0 .. t_{n-1} (maximum first, exp_det, 64 accumulators per piece of `chunk`, one division)
+//   out[r, j]: the elements are cut into pieces of `chunk`; a piece starts at +0.0 and takes acc = fma(p_i, v[c_i, j], acc) for
+//          i ascending; the piece sums are added in piece order (the first piece's sum is the start).  An empty row is +0.0.
+// No atomics; every output is written once; neither `group`, `short_max`, `max_len` nor the launch geometry changes a bit.
+//
+// Three forms, chosen per row from its length n:
+//   short  0 <= n <= short_max (<= 64): a sub-group of G = 8 | 16 | 32 | 64 lanes owns (row, head).  The lanes run along D for
+//          the dot products - lane u holds the accumulators u, u + G, .. (64 / G registers), four elements at a time so that
+//          their k rows are in flight together -, the score of element i lands in lane i mod G, register i / G, where A14's
+//          short form finds it; then the lanes run along Dv, p_i and c_i broadcast by shuffle, four v rows in flight.
+//   wide   short_max < n <= chunk: a wave (a workgroup of its own) per (row, head); the scores are parked in LDS (chunk values),
+//          A14's wide form runs over them in place, then the same output loop.
+//   long   n > chunk: unfused through the workspace, in pieces of `chunk` elements found by windows as in csrc/softmax.hip.
+//          Six launches that each END before the next reads what it wrote: piece scores and maxima, row maxima, piece sums,
+//          row sums (piece order), piece outputs, row outputs (piece order).
+#include "common.h"
+#include "exp_det.h"
+
+#include <algorithm>
+#include <limits>
+
+#define ATTENTION_MAX_CHUNK 1024
+
+namespace spamd {
+
+template <typename T>
+__device__ __forceinline__ T at_nmax(T a, T b) {   // NaN wins from either side
+  return (a > b || a != a) ? a : b;
+}
+
+template <typename T, int W>
+__device__ __forceinline__ T at_xmax(T m) {
+#pragma unroll
+  for (int h = W / 2; h >= 1; h /= 2) m = at_nmax(m, __shfl_xor(m, h, W));
+  return m;
+}
+
+// a[l] = a[l] + a[l ^ h], h = W / 2 .. 1: every lane ends with the bits of the halving fold (the sum of two is commutative)
+template <typename T, int W>
+__device__ __forceinline__ T at_xsum(T s) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int h = W / 2; h >= 1; h /= 2) s = s + __shfl_xor(s, h, W);
+  return s;
+}
+
+template <typename T>
+__device__ __forceinline__ T at_fma(T a, T b, T c) {
+  if constexpr (sizeof(T) == 4) return __builtin_fmaf(a, b, c);
+  else return __builtin_fma(a, b, c);
+}
+
+template <typename T>
+__device__ __forceinline__ T at_neg_inf() {
+  return -std::numeric_limits<T>::infinity();
+}
+
+template <typename T, typename I>
+struct AtIn {
+  const I* ptr;
+  const I* idx;
+  const T* sv;
+  const T* q;
+  const T* k;
+  const T* v;
+  int64_t qp, qh, kp, kh, vp, vh;   // row pitch and head stride, in elements
+  int64_t M, H;   // H: heads of this launch (at most 65535: grid.y), the host offsets the pointers for more
+  int D, Dv;
+  T scale;
+  bool has_scale;
+  T* out;
+  __device__ __forceinline__ T score(T s, T w) const {
+#pragma clang fp contract(off)
+    const T t = s * w;
+    return has_scale ? scale * t : t;
+  }
+};
+
+// one block of 64 elements (from e0) of four dot products: a[e][m] = fma(q[l], k_e[l], a[e][m]) at l = e0 + sub + G m.  TAIL: the
+// block may reach past D - such an element is read at D - 1 and not used (no branch around a load)
+template <typename T, int G, bool TAIL>
+__device__ __forceinline__ void at_dot4_block(const T* __restrict__ q, const T* __restrict__ k0, const T* __restrict__ k1,
+                                              const T* __restrict__ k2, const T* __restrict__ k3, int D, int e0, int sub,
+                                              T (&a)[4][64 / G]) {
+#pragma clang fp contract(off)
+  constexpr int V = 64 / G;
+  constexpr int MB = sizeof(T) * V > 32 ? V / 2 : V;   // loads in flight per k row: at most 32 bytes a lane
+#pragma unroll
+  for (int m0 = 0; m0 < V; m0 += MB) {
+    T qv[MB], kv[4][MB];
+#pragma unroll
+    for (int m = 0; m < MB; ++m) {
+      const int l = e0 + sub + G * (m0 + m);
+      const int e = TAIL ? std::min(l, D - 1) : l;
+      qv[m] = q[e];
+      kv[0][m] = k0[e];
+      kv[1][m] = k1[e];
+      kv[2][m] = k2[e];
+      kv[3][m] = k3[e];
+    }
+#pragma unroll
+    for (int m = 0; m < MB; ++m) {
+      const bool in = !TAIL || e0 + sub + G * (m0 + m) < D;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const T f = at_fma(qv[m], kv[e][m], a[e][m0 + m]);
+        a[e][m0 + m] = in ? f : a[e][m0 + m];
+      }
+    }
+  }
+}
+
+// four dot products of the row `q` with the rows k0 .. k3 by a sub-group of G lanes (lane `sub`): every lane returns all four
+template <typename T, int G>
+__device__ __forceinline__ void at_dot4(const T* __restrict__ q, const T* __restrict__ k0, const T* __restrict__ k1,
+                                        const T* __restrict__ k2, const T* __restrict__ k3, int D, int sub, T (&w)[4]) {
+#pragma clang fp contract(off)
+  constexpr int V = 64 / G;
+  T a[4][V];
+#pragma unroll
+  for (int e = 0; e < 4; ++e)
+#pragma unroll
+    for (int m = 0; m < V; ++m) a[e][m] = T(0);
+  int e0 = 0;
+  for (; e0 + 64 <= D; e0 += 64) at_dot4_block<T, G, false>(q, k0, k1, k2, k3, D, e0, sub, a);
+  if (e0 < D) at_dot4_block<T, G, true>(q, k0, k1, k2, k3, D, e0, sub, a);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+#pragma unroll
+    for (int hv = V / 2; hv >= 1; hv /= 2)   // h = 32 .. G: both accumulators live in this lane
+#pragma unroll
+      for (int m = 0; m < hv; ++m) a[e][m] = a[e][m] + a[e][m + hv];
+    w[e] = at_xsum<T, G>(a[e][0]);
+  }
+}
+
+// acc[c] = fma(p_e, v_e[j], acc[c]) for e = 0 .. 3 in order, at the columns j = jb + sub + G c of this lane.  EDGE: fewer than
+// four elements are live (`left`), or the block reaches past Dv - such a column is read at Dv - 1 and never stored
+template <typename T, int G, bool EDGE>
+__device__ __forceinline__ void at_out4(const T (&pp)[4], const T* const (&vr)[4], int jb, int sub, int Dv, int left,
+                                        T (&acc)[64 / G]) {
+#pragma clang fp contract(off)
+  constexpr int V = 64 / G;
+  constexpr int MB = sizeof(T) * V > 32 ? V / 2 : V;   // loads in flight per v row: at most 32 bytes a lane
+#pragma unroll
+  for (int c0 = 0; c0 < V; c0 += MB) {
+    T vv[4][MB];
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+#pragma unroll
+      for (int c = 0; c < MB; ++c) {
+        const int j = jb + sub + G * (c0 + c);
+        vv[e][c] = vr[e][EDGE ? std::min(j, Dv - 1) : j];
+      }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const bool live = !EDGE || e < left;
+#pragma unroll
+      for (int c = 0; c < MB; ++c) {
+        const T f = at_fma(pp[e], vv[e][c], acc[c0 + c]);
+        acc[c0 + c] = live ? f : acc[c0 + c];
+      }
+    }
+  }
+}
+
+// ---- short: a sub-group of G lanes per (row, head) ----------------------------------------------------------------------------
+template <typename T, typename I, int G>
+__global__ void __launch_bounds__(256)
+at_short_kernel(AtIn<T, I> in, int64_t short_max) {
+#pragma clang fp contract(off)
+  constexpr int V = 64 / G;
+  constexpr int GPB = 256 / G;
+  const int sub = threadIdx.x % G;
+  {
+    const int64_t head = blockIdx.y;
+    const T* __restrict__ kh = in.k + head * in.kh;
+    const T* __restrict__ vh = in.v + head * in.vh;
+    for (int64_t row = (int64_t)blockIdx.x * GPB + threadIdx.x / G; row < in.M; row += (int64_t)gridDim.x * GPB) {
+      const int64_t b = (int64_t)in.ptr[row];
+      const int n = (int)std::min<int64_t>((int64_t)in.ptr[row + 1] - b, 65);
+      if (n > short_max) continue;   // (the same in every lane of the sub-group)
+      const T* __restrict__ qrow = in.q + head * in.qh + row * in.qp;
+      T t[V], sv[V];
+      int64_t col[V];
+#pragma unroll
+      for (int r = 0; r < V; ++r) {
+        const int i = sub + r * G;
+        col[r] = 0;
+        sv[r] = T(0);
+        t[r] = at_neg_inf<T>();
+        if (i < n) {
+          col[r] = (int64_t)in.idx[b + i];
+          sv[r] = in.sv[b + i];
+        }
+      }
+      // phase 1: the scores, four elements at a time; r is unrolled so that no register array is indexed
+#pragma unroll
+      for (int r = 0; r < V; ++r) {
+        const int cnt = n - r * G;   // elements of register r: the lanes 0 .. min(cnt, G) - 1
+        for (int ii = 0; ii < G && ii < cnt; ii += 4) {
+          const T* kr[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) kr[e] = kh + __shfl(col[r], ii + e < cnt ? ii + e : ii, G) * in.kp;
+          T w[4];
+          at_dot4<T, G>(qrow, kr[0], kr[1], kr[2], kr[3], in.D, sub, w);
+          T mine = w[0];
+#pragma unroll
+          for (int e = 1; e < 4; ++e) mine = sub == ii + e ? w[e] : mine;
+          mine = in.score(sv[r], mine);
+          t[r] = sub >= ii && sub < ii + 4 && sub < cnt ? mine : t[r];   // the lanes that hold these four elements
+        }
+      }
+      // phase 2: A14's short form on the registers
+      T m = at_neg_inf<T>();
+#pragma unroll
+      for (int r = 0; r < V; ++r)
+        if (sub + r * G < n) m = at_nmax(m, t[r]);
+      m = at_xmax<T, G>(m);
+      T a[V];
+#pragma unroll
+      for (int r = 0; r < V; ++r) {
+        t[r] = sub + r * G < n ? exp_det(t[r] - m) : T(0);
+        a[r] = t[r];
+      }
+#pragma unroll
+      for (int hv = V / 2; hv >= 1; hv /= 2)
+#pragma unroll
+        for (int r = 0; r < hv; ++r) a[r] = a[r] + a[r + hv];
+      const T s = at_xsum<T, G>(a[0]);
+#pragma unroll
+      for (int r = 0; r < V; ++r) t[r] = t[r] / s;
+      // phase 3: the output row, 64 columns at a time (lane u: the columns u, u + G, ..), four v rows in flight
+      T* __restrict__ orow = in.out + (head * in.M + row) * in.Dv;
+      for (int jb = 0; jb < in.Dv; jb += 64) {
+        T acc[V];
+#pragma unroll
+        for (int c = 0; c < V; ++c) acc[c] = T(0);
+#pragma unroll
+        for (int r = 0; r < V; ++r) {
+          const int cnt = n - r * G;
+          for (int ii = 0; ii < G && ii < cnt; ii += 4) {
+            T pp[4];
+            const T* vr[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const int src = ii + e < cnt ? ii + e : ii;
+              pp[e] = __shfl(t[r], src, G);
+              vr[e] = vh + __shfl(col[r], src, G) * in.vp;
+            }
+            if (ii + 4 <= cnt && jb + 64 <= in.Dv) at_out4<T, G, false>(pp, vr, jb, sub, in.Dv, cnt - ii, acc);
+            else at_out4<T, G, true>(pp, vr, jb, sub, in.Dv, cnt - ii, acc);
+          }
+        }
+#pragma unroll
+        for (int c = 0; c < V; ++c) {
+          const int j = jb + sub + G * c;
+          if (j < in.Dv) orow[j] = acc[c];
+        }
+      }
+    }
+  }
+}
+
+// ---- the wave's output loop: acc = fma(p_i, v[c_i, j], acc), i ascending, from +0.0, for the column j of this lane -----------
+// `p(i)` and `c(i)` give element i's probability and column to every lane (wave-uniform values)
+template <typename T, typename P, typename C>
+__device__ __forceinline__ T at_wave_out(const T* __restrict__ vh, int64_t vp, int j, bool live, int cnt, P p, C c) {
+#pragma clang fp contract(off)
+  T acc = T(0);
+  for (int i = 0; i < cnt; i += 4) {
+    T pp[4], vv[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int src = i + e < cnt ? i + e : i;
+      pp[e] = p(src);
+      vv[e] = live ? vh[c(src) * vp + j] : T(0);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (i + e < cnt) acc = at_fma(pp[e], vv[e], acc);
+  }
+  return acc;
+}
+
+// ---- wide: a wave (one workgroup) per (row, head), the scores in LDS ------------------------------------------------------------
+template <typename T, typename I>
+__global__ void __launch_bounds__(64)
+at_wide_kernel(AtIn<T, I> in, int64_t above, int64_t upto) {
+#pragma clang fp contract(off)
+  extern __shared__ __attribute__((aligned(16))) unsigned char at_smem[];
+  T* __restrict__ lds = reinterpret_cast<T*>(at_smem);   // `upto` values
+  const int lane = threadIdx.x;
+  {
+    const int64_t head = blockIdx.y;
+    const T* __restrict__ kh = in.k + head * in.kh;
+    const T* __restrict__ vh = in.v + head * in.vh;
+    for (int64_t base = (int64_t)blockIdx.x * 64; base < in.M; base += (int64_t)gridDim.x * 64) {
+      const int64_t mine = base + lane;
+      int64_t mb = 0, mn = 0;
+      if (mine < in.M) {
+        mb = (int64_t)in.ptr[mine];
+        mn = (int64_t)in.ptr[mine + 1] - mb;
+      }
+      unsigned long long todo = __ballot(mn > above && mn <= upto);
+      while (todo) {   // wave-uniform: all 64 lanes stay together
+        const int src = __builtin_ctzll(todo);
+        todo &= todo - 1;
+        const int64_t row = base + src, b = wave_bcast(mb, src);
+        const int n = (int)wave_bcast(mn, src);
+        const T* __restrict__ qrow = in.q + head * in.qh + row * in.qp;
+        const I* __restrict__ idx = in.idx + b;
+        for (int i = 0; i < n; i += 4) {
+          const T* kr[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) kr[e] = kh + (int64_t)idx[i + e < n ? i + e : i] * in.kp;
+          T w[4];
+          at_dot4<T, 64>(qrow, kr[0], kr[1], kr[2], kr[3], in.D, lane, w);
+          if (lane == 0) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+              if (i + e < n) lds[i + e] = in.score(in.sv[b + i + e], w[e]);
+          }
+        }
+        __syncthreads();
+        // A14's wide form: lane u owns the elements u, u + 64, ..
+        T m = at_neg_inf<T>();
+        for (int x = lane; x < n; x += 64) m = at_nmax(m, lds[x]);
+        m = at_xmax<T, 64>(m);
+        T acc = T(0);
+        for (int x = lane; x < n; x += 64) {
+          const T e = exp_det(lds[x] - m);
+          lds[x] = e;
+          acc = acc + e;
+        }
+        const T s = at_xsum<T, 64>(acc);
+        for (int x = lane; x < n; x += 64) lds[x] = lds[x] / s;
+        __syncthreads();
+        T* __restrict__ orow = in.out + (head * in.M + row) * in.Dv;
+        for (int jb = 0; jb < in.Dv; jb += 64) {
+          const int j = jb + lane;
+          const T o = at_wave_out<T>(vh, in.vp, j, j < in.Dv, n, [&](int x) { return lds[x]; },
+                                     [&](int x) { return (int64_t)idx[x]; });
+          if (j < in.Dv) orow[j] = o;
+        }
+        __syncthreads();   // the next row writes the scores again
+      }
+    }
+  }
+}
+
+// ---- long: pieces ------------------------------------------------------------------------------------------------------------------
+// last r in [0, M] with ptr[r] <= pos (ptr[0] = 0 <= pos): the non-empty row that holds pos when pos < nnz
+template <typename I>
+__device__ __forceinline__ int64_t at_row_of(const I* __restrict__ ptr, int64_t M, int64_t pos) {
+  int64_t lo = 0, hi = M;
+  while (lo < hi) {
+    const int64_t mid = lo + (hi - lo + 1) / 2;
+    if ((int64_t)ptr[mid] <= pos) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+// the workspace slot of the piece of a long row (first position b) that starts at position s: window g = s / chunk holds at
+// most two piece starts of long rows (csrc/mttkrp.hip has the argument) - slots 2g and 2g + 1
+__device__ __forceinline__ int64_t at_slot(int64_t b, int64_t s, int64_t chunk) {
+  return 2 * (s / chunk) + (s == b && b % chunk != 0 ? 1 : 0);
+}
+
+// workspace of one head, in values: the scores (nnz, at stored positions), four arrays of 2 * nwin - piece maxima, piece sums,
+// row maxima and row sums (the last two at the slot of the row's first piece) -, the piece outputs (2 * nwin rows of Dv)
+__host__ __device__ __forceinline__ int64_t at_ws_values(int64_t nnz, int64_t nwin, int64_t Dv) {
+  return nnz + 8 * nwin + 2 * nwin * Dv;
+}
+
+template <typename T, typename I, int PHASE>
+__device__ __forceinline__ void at_piece(const AtIn<T, I>& in, int64_t head, int64_t row, int64_t b, int64_t s, int64_t e,
+                                         int64_t chunk, int64_t nnz, int64_t nwin, int lane, T* __restrict__ ws) {
+#pragma clang fp contract(off)
+  T* __restrict__ sc = ws;
+  T* __restrict__ st = ws + nnz;
+  T* __restrict__ part = ws + nnz + 8 * nwin;
+  const int64_t slot = at_slot(b, s, chunk), slot0 = at_slot(b, b, chunk);
+  if (PHASE == 0) {
+    const T* __restrict__ kh = in.k + head * in.kh;
+    const T* __restrict__ qrow = in.q + head * in.qh + row * in.qp;
+    T m = at_neg_inf<T>();
+    for (int64_t x = s; x < e; x += 4) {
+      const T* kr[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) kr[u] = kh + (int64_t)in.idx[x + u < e ? x + u : x] * in.kp;
+      T w[4];
+      at_dot4<T, 64>(qrow, kr[0], kr[1], kr[2], kr[3], in.D, lane, w);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (x + u < e) {
+          const T t = in.score(in.sv[x + u], w[u]);
+          m = at_nmax(m, t);
+          if (lane == 0) sc[x + u] = t;
+        }
+      }
+    }
+    if (lane == 0) st[slot] = m;
+  } else if (PHASE == 1) {
+    const T m = st[4 * nwin + slot0];
+    T acc = T(0);
+    for (int64_t x = s + lane; x < e; x += 64) acc = acc + exp_det(sc[x] - m);
+    acc = at_xsum<T, 64>(acc);
+    if (lane == 0) st[2 * nwin + slot] = acc;
+  } else {
+    const T* __restrict__ vh = in.v + head * in.vh;
+    const T m = st[4 * nwin + slot0], sum = st[6 * nwin + slot0];
+    for (int jb = 0; jb < in.Dv; jb += 64) {
+      const int j = jb + lane;
+      const bool live = j < in.Dv;
+      T acc = T(0);
+      for (int64_t x0 = s; x0 < e; x0 += 64) {   // 64 probabilities, one per lane, then broadcast one after the other
+        const int cnt = (int)std::min<int64_t>(e - x0, 64);
+        T p = T(0);
+        int64_t c = 0;
+        if (lane < cnt) {
+          p = exp_det(sc[x0 + lane] - m) / sum;
+          c = (int64_t)in.idx[x0 + lane];
+        }
+        for (int i = 0; i < cnt; i += 4) {
+          T pp[4], vv[4];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const int src = i + u < cnt ? i + u : i;
+            pp[u] = wave_bcast(p, src);
+            vv[u] = live ? vh[wave_bcast(c, src) * in.vp + j] : T(0);
+          }
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+            if (i + u < cnt) acc = at_fma(pp[u], vv[u], acc);
+        }
+      }
+      if (live) part[slot * (int64_t)in.Dv + j] = acc;
+    }
+  }
+}
+
+template <typename T, typename I, int PHASE>
+__global__ void __launch_bounds__(256)
+at_piece_kernel(AtIn<T, I> in, int64_t nnz, int64_t chunk, int64_t nwin, T* __restrict__ ws_all) {
+  const int lane = threadIdx.x & 63;
+  const int64_t M = in.M;
+  {
+    const int64_t head = blockIdx.y;
+    T* __restrict__ ws = ws_all + head * at_ws_values(nnz, nwin, in.Dv);
+    for (int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); g < nwin; g += (int64_t)gridDim.x * 4) {
+      const int64_t lo = g * chunk;
+      const int64_t hi = lo + chunk < nnz ? lo + chunk : nnz;
+      const int64_t r0 = at_row_of(in.ptr, M, lo);   // lo < nnz: r0 < M and the row is not empty
+      {
+        const int64_t b0 = (int64_t)in.ptr[r0], e0 = (int64_t)in.ptr[r0 + 1];
+        if (e0 - b0 > chunk) {
+          const int64_t s = b0 + (lo - b0 + chunk - 1) / chunk * chunk;   // the one piece start of this row in [lo, lo + chunk)
+          if (s < hi && s < e0)
+            at_piece<T, I, PHASE>(in, head, r0, b0, s, s + chunk < e0 ? s + chunk : e0, chunk, nnz, nwin, lane, ws);
+        }
+      }
+      const int64_t r1 = at_row_of(in.ptr, M, hi - 1);
+      if (r1 > r0) {   // starts inside the window; only the last such row can be longer than the window
+        const int64_t b1 = (int64_t)in.ptr[r1], e1 = (int64_t)in.ptr[r1 + 1];
+        if (e1 - b1 > chunk) at_piece<T, I, PHASE>(in, head, r1, b1, b1, b1 + chunk, chunk, nnz, nwin, lane, ws);
+      }
+    }
+  }
+}
+
+// PHASE 0: row maxima from the piece maxima; PHASE 1: row sums, the piece sums added one after the other in piece order;
+// PHASE 2: output rows, the piece outputs added one after the other in piece order
+template <typename T, typename I, int PHASE>
+__global__ void __launch_bounds__(256)
+at_join_kernel(AtIn<T, I> in, int64_t nnz, int64_t chunk, int64_t nwin, T* __restrict__ ws_all) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & 63;
+  const int64_t nwaves = (int64_t)gridDim.x * 4;
+  {
+    const int64_t head = blockIdx.y;
+    T* __restrict__ st = ws_all + head * at_ws_values(nnz, nwin, in.Dv) + nnz;
+    const T* __restrict__ part = st + 8 * nwin;
+    for (int64_t base = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64; base < in.M; base += nwaves * 64) {
+      const int64_t mine = base + lane;
+      int64_t mb = 0, mn = 0;
+      if (mine < in.M) {
+        mb = (int64_t)in.ptr[mine];
+        mn = (int64_t)in.ptr[mine + 1] - mb;
+      }
+      unsigned long long todo = __ballot(mn > chunk);
+      while (todo) {
+        const int src = __builtin_ctzll(todo);
+        todo &= todo - 1;
+        const int64_t b = wave_bcast(mb, src), n = wave_bcast(mn, src);
+        const int64_t np = (n + chunk - 1) / chunk;
+        const int64_t slot0 = at_slot(b, b, chunk);
+        if (PHASE == 0) {
+          T m = at_neg_inf<T>();
+          for (int64_t k = lane; k < np; k += 64) m = at_nmax(m, st[at_slot(b, b + k * chunk, chunk)]);
+          m = at_xmax<T, 64>(m);
+          if (lane == 0) st[4 * nwin + slot0] = m;
+        } else if (PHASE == 1) {
+          T s = T(0);
+          for (int64_t k0 = 0; k0 < np; k0 += 64) {
+            const int cnt = (int)(np - k0 < 64 ? np - k0 : 64);
+            const T v = lane < cnt ? st[2 * nwin + at_slot(b, b + (k0 + lane) * chunk, chunk)] : T(0);
+            for (int u = 0; u < cnt; ++u) {
+              const T pv = wave_bcast(v, u);
+              s = (k0 + u == 0) ? pv : s + pv;
+            }
+          }
+          if (lane == 0) st[6 * nwin + slot0] = s;
+        } else {
+          T* __restrict__ orow = in.out + (head * in.M + base + src) * in.Dv;
+          for (int j = lane; j < in.Dv; j += 64) {
+            T s = part[slot0 * (int64_t)in.Dv + j];
+            for (int64_t k = 1; k < np; ++k) s = s + part[at_slot(b, b + k * chunk, chunk) * (int64_t)in.Dv + j];
+            orow[j] = s;
+          }
+        }
+      }
+    }
+  }
+}
+
+static unsigned at_grid(int64_t items, int64_t per_block) {
+  return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(items, per_block), (int64_t)1 << 20));
+}
+
+template <typename T, typename I>
+static int attention_typed(AtIn<T, I> in, int64_t nnz, int group, int64_t short_max, int64_t chunk, int64_t max_len, void* ws_,
+                           hipStream_t st) {
+  const unsigned gy = (unsigned)in.H;
+  {   // (always: the rows without a stored element are written here)
+#define AT_SHORT(G) \
+  hipLaunchKernelGGL((at_short_kernel<T, I, G>), dim3(at_grid(in.M, 256 / G), gy), dim3(256), 0, st, in, short_max)
+    if (group == 8) AT_SHORT(8);
+    else if (group == 16) AT_SHORT(16);
+    else if (group == 32) AT_SHORT(32);
+    else AT_SHORT(64);
+#undef AT_SHORT
+    if (int rc = launch_status()) return rc;
+  }
+  if (std::min(max_len, chunk) > short_max) {
+    hipLaunchKernelGGL((at_wide_kernel<T, I>), dim3(at_grid(in.M, 64), gy), dim3(64), (size_t)chunk * sizeof(T), st, in, short_max,
+                       chunk);
+    if (int rc = launch_status()) return rc;
+  }
+  if (max_len > chunk) {
+    T* ws = (T*)ws_;
+    const int64_t nwin = ceil_div(nnz, chunk);
+    const dim3 pg(at_grid(nwin, 4), gy), jg(at_grid(in.M, 256), gy);
+    hipLaunchKernelGGL((at_piece_kernel<T, I, 0>), pg, dim3(256), 0, st, in, nnz, chunk, nwin, ws);
+    if (int rc = launch_status()) return rc;
+    hipLaunchKernelGGL((at_join_kernel<T, I, 0>), jg, dim3(256), 0, st, in, nnz, chunk, nwin, ws);
+    if (int rc = launch_status()) return rc;
+    hipLaunchKernelGGL((at_piece_kernel<T, I, 1>), pg, dim3(256), 0, st, in, nnz, chunk, nwin, ws);
+    if (int rc = launch_status()) return rc;
+    hipLaunchKernelGGL((at_join_kernel<T, I, 1>), jg, dim3(256), 0, st, in, nnz, chunk, nwin, ws);
+    if (int rc = launch_status()) return rc;
+    hipLaunchKernelGGL((at_piece_kernel<T, I, 2>), pg, dim3(256), 0, st, in, nnz, chunk, nwin, ws);
+    if (int rc = launch_status()) return rc;
+    hipLaunchKernelGGL((at_join_kernel<T, I, 2>), jg, dim3(256), 0, st, in, nnz, chunk, nwin, ws);
+    if (int rc = launch_status()) return rc;
+  }
+  return 0;
+}
+
+template <typename T, typename I>
+static int attention_in(int64_t M, int64_t nnz, int64_t H, int64_t D, int64_t Dv, const void* ptr, const void* idx, const void* sv,
+                        const void* q, int64_t qp, int64_t qh, const void* k, int64_t kp, int64_t kh, const void* v, int64_t vp,
+                        int64_t vh, int has_scale, double scale, int group, int64_t short_max, int64_t chunk, int64_t max_len,
+                        void* ws, void* out, hipStream_t st) {
+  const int64_t ws_head = max_len > chunk ? at_ws_values(nnz, ceil_div(nnz, chunk), Dv) : 0;
+  for (int64_t h0 = 0; h0 < H; h0 += 65535) {   // a head per grid.y: at most 65535 of them in one launch
+    AtIn<T, I> in{(const I*)ptr, (const I*)idx, (const T*)sv, (const T*)q + h0 * qh, (const T*)k + h0 * kh, (const T*)v + h0 * vh,
+                  qp, qh, kp, kh, vp, vh, M, std::min<int64_t>(H - h0, 65535), (int)D, (int)Dv, (T)scale, has_scale != 0,
+                  (T*)out + h0 * M * Dv};
+    if (int rc = attention_typed<T, I>(in, nnz, group, short_max, chunk, max_len, ws ? (T*)ws + h0 * ws_head : nullptr, st)) return rc;
+  }
+  return 0;
+}
+
+}  // namespace spamd
+
+using namespace spamd;
+
+extern "C" int64_t spamd_attention_ws_bytes(int val_dtype, int64_t nnz, int64_t H, int64_t Dv, int64_t chunk) {
+  const int64_t esz = val_dtype == SPAMD_F32 ? 4 : (val_dtype == SPAMD_F64 ? 8 : 0);
+  if (!esz) return SPAMD_ETYPE;
+  if (nnz < 0 || H < 0 || Dv < 0 || chunk < 64 || chunk > ATTENTION_MAX_CHUNK || chunk % 64) return SPAMD_EINVAL;
+  if (nnz <= chunk) return 0;
+  return H * at_ws_values(nnz, ceil_div(nnz, chunk), Dv) * esz;
+}
+
+extern "C" int spamd_attention(int val_dtype, int idx_dtype, int64_t M, int64_t N, int64_t nnz, int64_t H, int64_t D, int64_t Dv,
+                               const void* s_ptr, const void* s_idx, const void* s_val, const void* q, int64_t q_pitch,
+                               int64_t q_head, const void* k, int64_t k_pitch, int64_t k_head, const void* v, int64_t v_pitch,
+                               int64_t v_head, int has_scale, double scale, int group, int64_t short_max, int64_t chunk,
+                               int64_t max_len, void* ws, int64_t ws_bytes, void* out, void* stream) {
+  if (val_dtype != SPAMD_F32 && val_dtype != SPAMD_F64) return SPAMD_ETYPE;
+  if (idx_dtype != SPAMD_I32 && idx_dtype != SPAMD_I64) return SPAMD_ETYPE;
+  if (M < 0 || N < 0 || nnz < 0 || H < 0 || D < 0 || Dv < 0 || max_len < 0 || max_len > nnz) return SPAMD_EINVAL;
+  if (D > INT32_MAX - 128 || Dv > INT32_MAX - 128) return SPAMD_EINVAL;   // (row widths are 32-bit in the kernels)
+  if (q_pitch < 0 || q_head < 0 || k_pitch < 0 || k_head < 0 || v_pitch < 0 || v_head < 0) return SPAMD_EINVAL;
+  if (group != 8 && group != 16 && group != 32 && group != 64) return SPAMD_EINVAL;
+  if (chunk < 64 || chunk > ATTENTION_MAX_CHUNK || chunk % 64 || short_max < 0 || short_max > 64) return SPAMD_EINVAL;
+  if (M == 0 || H == 0 || Dv == 0) return 0;
+  if (!out || !s_ptr) return SPAMD_EINVAL;
+  if (nnz > 0 && (!s_idx || !s_val || !k || !v || (D > 0 && !q))) return SPAMD_EINVAL;
+  if (max_len > chunk && (!ws || ws_bytes < spamd_attention_ws_bytes(val_dtype, nnz, H, Dv, chunk))) return SPAMD_EWS;
+  hipStream_t st = (hipStream_t)stream;
+  SPAMD_DISPATCH_IDX(idx_dtype, I, {
+    if (val_dtype == SPAMD_F32)
+      return attention_in<float, I>(M, nnz, H, D, Dv, s_ptr, s_idx, s_val, q, q_pitch, q_head, k, k_pitch, k_head, v, v_pitch,
+                                    v_head, has_scale, scale, group, short_max, chunk, max_len, ws, out, st);
+    return attention_in<double, I>(M, nnz, H, D, Dv, s_ptr, s_idx, s_val, q, q_pitch, q_head, k, k_pitch, k_head, v, v_pitch,
+                                   v_head, has_scale, scale, group, short_max, chunk, max_len, ws, out, st);
+  })
+  return SPAMD_ETYPE;
+}
