@@ -319,16 +319,21 @@ int spamd_csx_swap8(int idx_dtype, int64_t n_major, int64_t n_minor, int64_t nnz
                    const void* indptr, void* out_data, void* out_indices, void* out_indptr, void* ws, int64_t ws_bytes,
                    void* stream);
 /* Stable radix sort of (key, value) int64 pairs on key bits [0, end_bit); keys must be >= 0.
- * Replaces `np.argsort(linear, kind="mergesort")` (core.py:1315).  Workspace from *_ws_bytes. */
+ * Replaces `np.argsort(linear, kind="mergesort")` (core.py:1315).  ws: spamd_sort_pairs_ws_bytes(n) bytes, which serve
+ * every end_bit (SPAMD_EWS when ws_bytes is smaller: nothing is launched). */
 int64_t spamd_sort_pairs_ws_bytes(int64_t n);
 int spamd_sort_pairs(int64_t n, const int64_t* keys_in, int64_t* keys_out, const int64_t* vals_in,
                      int64_t* vals_out, int end_bit, void* ws, int64_t ws_bytes, void* stream);
-/* The same stable sort carrying a 4- or 8-byte VALUE as payload (used by SpGEMM's expand-sort-compress). */
+/* The same stable sort carrying a 4- or 8-byte VALUE as payload (used by SpGEMM's expand-sort-compress).
+ * ws: spamd_sort_kv_ws_bytes(val_bytes, n) bytes (SPAMD_EWS when ws_bytes is smaller). */
 int64_t spamd_sort_kv_ws_bytes(int val_bytes, int64_t n);
 int spamd_sort_kv(int val_bytes, int64_t n, const int64_t* keys_in, int64_t* keys_out, const void* vals_in,
                   void* vals_out, int end_bit, void* ws, int64_t ws_bytes, void* stream);
 int spamd_iota(int64_t n, int64_t* out, void* stream);
-/* out[i] = in[0] + ... + in[i-1] for i in [0, n]; both arrays hold n+1 entries (in[n] ignored). */
+/* out[i] = in[0] + ... + in[i-1] for i in [0, n]; both arrays hold n+1 entries (in[n] ignored).
+ * spamd_scan_ws_bytes(n) is the workspace of spamd_exclusive_scan(n, ...), i.e. of a scan over the n + 1 items it
+ * processes - pass the same n to both.  Arrays of at most 16384 entries are scanned by one workgroup and take no
+ * workspace; beyond that, SPAMD_EWS when ws_bytes is smaller than the query's result (nothing is launched). */
 int64_t spamd_scan_ws_bytes(int64_t n);
 int spamd_exclusive_scan(int64_t n, const int64_t* in, int64_t* out, void* ws, int64_t ws_bytes, void* stream);
 /* astype between F32/F64/I32/I64/U8 (C-cast, NumPy "unsafe"; to U8 = x != 0) */

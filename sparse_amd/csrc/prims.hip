@@ -12,6 +12,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "div_recip.h"
 #include <rocprim/rocprim.hpp>
 
 namespace spamd {
@@ -26,18 +27,7 @@ struct DimPack {
   int32_t n;
 };
 
-// floor(r / d) for r < 2^52 through the FP64 pipe: the truncated product with 1/d is off by at most one either way
-// (r and the quotient are exact doubles, 1/d carries 2^-53 relative error), two compares repair it.  A 64-bit integer
-// division is ~100 emulated instructions on CDNA; this is ~10, and every key <-> coordinate conversion does one per
-// dimension per stored element.
-template <typename U>
-__device__ __forceinline__ U div_recip(U r, U d, double inv) {
-  U q = (U)((double)r * inv);
-  const U back = q * d;
-  if (back > r) --q;
-  else if (r - back >= d) ++q;
-  return q;
-}
+// (div_recip, the reciprocal division of the key <-> coordinate conversions below: div_recip.h)
 
 static inline unsigned grid_for(int64_t n, int per_thread = 1) {
   int64_t b = ceil_div(n, (int64_t)256 * per_thread);
@@ -640,6 +630,10 @@ extern "C" int spamd_sort_pairs(int64_t n, const int64_t* keys_in, int64_t* keys
                                 int64_t* vals_out, int end_bit, void* ws, int64_t ws_bytes, void* stream) {
   if (n < 0 || end_bit < 1 || end_bit > 64) return SPAMD_EINVAL;
   if (n == 0) return 0;
+  // (rocPRIM does not check the size it is handed)
+  const int64_t need = spamd_sort_pairs_ws_bytes(n);
+  if (need < 0) return (int)-need;
+  if (!ws || ws_bytes < need) return SPAMD_EWS;
   size_t bytes = (size_t)ws_bytes;
   hipError_t e = spamd::sort_pairs_tuned(ws, bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, (unsigned)end_bit,
                                          (hipStream_t)stream);
@@ -658,6 +652,10 @@ extern "C" int spamd_sort_kv(int val_bytes, int64_t n, const int64_t* keys_in, i
                              void* vals_out, int end_bit, void* ws, int64_t ws_bytes, void* stream) {
   if (n < 0 || end_bit < 1 || end_bit > 64) return SPAMD_EINVAL;
   if (n == 0) return 0;
+  if (val_bytes != 4 && val_bytes != 8) return SPAMD_ETYPE;
+  const int64_t need = spamd_sort_kv_ws_bytes(val_bytes, n);
+  if (need < 0) return (int)-need;
+  if (!ws || ws_bytes < need) return SPAMD_EWS;
   size_t bytes = (size_t)ws_bytes;
   hipError_t e;
   if (val_bytes == 8)
@@ -678,10 +676,12 @@ extern "C" int spamd_iota(int64_t n, int64_t* out, void* stream) {
   return launch_status();
 }
 
+// workspace of spamd_exclusive_scan(n, ...): the scan runs over n + 1 items (out[n] is the total), and rocPRIM's storage grows
+// with the number of blocks those items take
 extern "C" int64_t spamd_scan_ws_bytes(int64_t n) {
   size_t bytes = 0;
   int64_t* p = nullptr;
-  hipError_t e = rocprim::exclusive_scan(nullptr, bytes, p, p, (int64_t)0, (size_t)(n > 0 ? n : 1),
+  hipError_t e = rocprim::exclusive_scan(nullptr, bytes, p, p, (int64_t)0, (size_t)(n > 0 ? n : 0) + 1,
                                          rocprim::plus<int64_t>(), (hipStream_t)0);
   if (e != hipSuccess) return -(int64_t)e;
   return (int64_t)bytes + 16;
@@ -696,6 +696,9 @@ extern "C" int spamd_exclusive_scan(int64_t n, const int64_t* in, int64_t* out, 
     hipLaunchKernelGGL(small_exclusive_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, in, out, (int)(n + 1));
     return launch_status();
   }
+  const int64_t need = spamd_scan_ws_bytes(n);   // (rocPRIM does not check the size it is handed)
+  if (need < 0) return (int)-need;
+  if (!ws || ws_bytes < need) return SPAMD_EWS;
   size_t bytes = (size_t)ws_bytes;
   hipError_t e = rocprim::exclusive_scan(ws, bytes, in, out, (int64_t)0, (size_t)(n + 1), rocprim::plus<int64_t>(),
                                          (hipStream_t)stream);

@@ -183,7 +183,8 @@ def test_rows_to_indptr_ignores_nothing_and_writes_in_bounds(sp):
     guard = torch.full((R + 1 + 64,), -7, dtype=torch.int64, device="cuda")
     ptr = _kernels.rows_to_indptr(rows, R)
     assert ptr.numel() == R + 1 and int(ptr[0]) == 0 and int(ptr[1]) == 2 and int(ptr[6]) == 3 and int(ptr[R]) <= 6
-    # a long empty stretch in front of the only populated rows (one thread used to fill it serially)
+    # a long empty stretch in front of the only populated rows: R > 8 nnz, so this is the binary-search kernel (the fill kernel's
+    # wave-wide stretches are pinned in test_prims_gpu.py)
     big = 3_000_000
     rows = torch.full((5000,), big - 1, dtype=torch.int64, device="cuda")
     ptr = _kernels.rows_to_indptr(rows, big)
