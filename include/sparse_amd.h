@@ -384,7 +384,15 @@ int spamd_ewise_select(int elem_bytes, int64_t n, const void* mask_u8, const voi
  *   spamd_merge_union(fill=1, ...) -> out_keys[total] (strictly increasing), out_vals[total].
  *   out = func(a or fill_a, b or fill_b); entries bit-identical to fill_out are dropped.
  *   op codes as spamd_ewise_binary (6 = power and 9-14, 67, 68 are not available here); *_bits = raw bit patterns
- *   of the fill values in val_dtype (fill_out in the output dtype: U8 for ops 32..40). */
+ *   of the fill values in val_dtype (fill_out in the output dtype: U8 for ops 32..40).
+ *   fill = 2 is the same union in a single pass: counts = nblocks + 2 int64 of workspace (zeroed by the call),
+ *   counts[nblocks + 1] receives the number of outputs, out_keys / out_vals hold na + nb elements.
+ *   Every form writes out_keys / out_vals [0, total) and nothing else: with room for na + nb elements, the elements from
+ *   `total` on are left as they were.  part[nblocks + 1]: part[p] = number of A items among the first min(p * tile, na + nb)
+ *   items of the merged order, equal keys taken from A first.
+ *   Returns before any launch or memset: SPAMD_EINVAL for na < 0 or nb < 0; 0 for na + nb == 0 (nothing is written);
+ *   SPAMD_ETYPE for a val_dtype other than F32 | F64 | I32 | I64 | U8, for op 6 (power) and for the bitwise ops 64..66 on
+ *   F32 | F64. */
 int64_t spamd_merge_num_blocks(int64_t na, int64_t nb);
 int spamd_merge_partition(int64_t na, const int64_t* ka, int64_t nb, const int64_t* kb, int64_t* part,
                           void* stream);
@@ -397,8 +405,11 @@ int spamd_merge_union(int fill, int op, int val_dtype, int64_t na, const int64_t
  * call.  ws = int64[3 + capacity], capacity >= spamd_merge_fused_blocks(na, nb), all zero before the first use; calls that
  * share a workspace must be ordered on one stream.  *total_dev (device) receives the number of outputs; total_host, if not
  * null, is pinned host memory mapped to the device that receives it too (system-scope release store) - the host may spin on
- * it.  out_keys / out_vals hold na + nb elements.  Replaces `_match_arrays` + the mask loop of `_Elemwise`,
- * _umath.py:53-92,576-654, for canonical same-shape operands. */
+ * it.  out_keys / out_vals hold na + nb elements; only [0, total) is written.  A workspace of exactly
+ * 3 + spamd_merge_fused_blocks(na, nb) words serves.  Returns before any launch (the workspace stays zero): SPAMD_EINVAL
+ * for na < 0, nb < 0, a null ws or total_dev, and for na + nb == 0 - the caller returns the empty result itself; SPAMD_ETYPE
+ * as spamd_merge_union.  Replaces `_match_arrays` + the mask loop of `_Elemwise`, _umath.py:53-92,576-654, for canonical
+ * same-shape operands. */
 /* tiles the fused form below runs (its workspace holds 3 + that many int64) */
 int64_t spamd_merge_fused_blocks(int64_t na, int64_t nb);
 int spamd_merge_union_fused(int op, int val_dtype, int64_t na, const int64_t* ka, const void* va, int64_t nb,
@@ -708,7 +719,9 @@ int spamd_cplx_fill(int val_dtype, int64_t n, void* out, double re, double im, v
  * counts = spamd_merge_num_blocks(na, nb) + 2 int64 of workspace (zeroed here), counts[nblocks + 1] receives the number of
  * outputs, out_keys / out_vals hold na + nb elements.  op as spamd_cplx_binary.  The fill values are passed by HOST
  * address: fill_a / fill_b point to one value of val_dtype, fill_out to one value of val_dtype (ops 0-3) or to one byte
- * (ops 36, 37); results bit-identical to *fill_out (both parts) are dropped. */
+ * (ops 36, 37); results bit-identical to *fill_out (both parts) are dropped.  Only out_keys / out_vals [0, total) are written.
+ * Returns before any launch or memset: SPAMD_EINVAL for na < 0, nb < 0, a null fill pointer or an op outside 0-3, 36, 37;
+ * SPAMD_ETYPE for a val_dtype other than C64 | C128; 0 for na + nb == 0. */
 int spamd_merge_union_complex(int op, int val_dtype, int64_t na, const int64_t* ka, const void* va, int64_t nb,
                               const int64_t* kb, const void* vb, const void* fill_a, const void* fill_b, const void* fill_out,
                               const int64_t* part, int64_t* counts, int64_t* out_keys, void* out_vals, void* stream);

@@ -381,14 +381,17 @@ extern "C" int spamd_merge_union(int fill, int op, int val_dtype, int64_t na, co
   const int64_t nblocks = spamd_merge_num_blocks(na, nb);
   if (nblocks == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
+  const bool to_bool = op >= 32 && op < 64;
+  // everything that is declined is declined before the workspace is touched
+  if (val_dtype != SPAMD_F32 && val_dtype != SPAMD_F64 && val_dtype != SPAMD_I32 && val_dtype != SPAMD_I64 && val_dtype != SPAMD_U8)
+    return SPAMD_ETYPE;
+  if (op >= 64 && (val_dtype == SPAMD_F32 || val_dtype == SPAMD_F64)) return SPAMD_ETYPE;
+  if (op == 6) return SPAMD_ETYPE;  // power: use the aligned-array path
   if (fill == 2) {
     hipError_t e = hipMemsetAsync(counts, 0, (size_t)(nblocks + 2) * sizeof(int64_t), s);
     if (e != hipSuccess) return (int)e;
   }
-  const bool to_bool = op >= 32 && op < 64;
-  if (op >= 64 && (val_dtype == SPAMD_F32 || val_dtype == SPAMD_F64)) return SPAMD_ETYPE;
-  if (op == 6) return SPAMD_ETYPE;  // power: use the aligned-array path
-#define MP_LAUNCH(T, O)                                                                                       \
+#define MP_LAUNCH(T, O)                                                                                      \
   do {                                                                                                        \
     if (fill == 2)                                                                                     \
       hipLaunchKernelGGL((mp_union_kernel<T, O, 2>), dim3((unsigned)nblocks), dim3(MP_THREADS), 0, s, op, ka,    \
