@@ -879,6 +879,57 @@ int spamd_attention(int val_dtype, int idx_dtype, int64_t M, int64_t N, int64_t 
                     int has_scale, double scale, int group, int64_t short_max, int64_t chunk, int64_t max_len, void* ws,
                     int64_t ws_bytes, void* out, void* stream);
 
+/* =======================================================================================
+ * A16  the backward pass of sparse attention (csrc/attention_grad.hip): from g = d loss / d out (H, M, Dv) of A15, for every
+ *   head, dq (H, M, D), dk (H, N, D) and dv (H, N, Dv).  The gradient with respect to the mask values is not computed.
+ *   The mask, q, k, v, has_scale and scale are A15's.  g has its own row pitch and head stride, last axis contiguous.  The
+ *   column grouping is state of the pattern alone, built by the caller: c_ptr (idx_dtype, N + 1 entries ascending from 0 to
+ *   nnz) bounds column c's elements in column order; c_perm (int64[nnz]) maps a position of the column order to a stored
+ *   position, ascending within a column (a stable grouping: well defined for unsorted rows too); c_row (idx_dtype, nnz) is
+ *   the row id of every element in column order.  dq, dk and dv are contiguous, of val_dtype.
+ *   Contract: every operation is rounded once (an fma counts as one; there is no EXACT variant); every element of dq, dk and
+ *   dv is written exactly once; no atomic touches a value; results are bitwise reproducible and depend neither on the launch
+ *   geometry nor on group / col_group / short_max / max_row / max_col.
+ *   Row pass - row r of one head, stored elements i = 0 .. n-1, columns c_i:
+ *     t_i, p_i  exactly A15's w_i, t_i and p_i: the same bits as spamd_attention computes for the same inputs and `chunk`
+ *     e_i   = dot(g[r], v[c_i]) by A15's 64 accumulators over Dv: a_l = fma(g[r][l + 64 j], v[c_i][l + 64 j], a_l) for j
+ *             ascending from +0.0, folded by halving, h = 32 .. 1
+ *     u_i   = p_i * e_i, one multiply
+ *     delta = the sum of the u_i in A14's order: pieces of `chunk`; in a piece accumulator l holds the piece's element l and
+ *             adds its elements l + 64, l + 128, .. in order (an accumulator without an element is +0.0); the fold by halving;
+ *             the piece sums added in piece order, the first piece's sum being the start
+ *     z_i   = p_i * (e_i - delta), one subtraction, then one multiply
+ *     y_i   = s_i * z_i, one multiply; has_scale != 0: y_i = (T)scale * y_i, one more
+ *     dq[r][j]: the elements are cut into pieces of `chunk`; a piece starts at +0.0 and takes acc = fma(y_i, k[c_i][j], acc)
+ *             for i ascending; the piece sums are added in piece order, the first piece's sum being the start
+ *   Column pass - column c of one head, its stored elements in stored order: positions pos_0 < .. < pos_{m-1}, rows r_i, cut
+ *   into pieces of `chunk` by the same rule:
+ *     dv[c][j]: acc = fma(p[pos_i], g[r_i][j], acc);   dk[c][j]: acc = fma(y[pos_i], q[r_i][j], acc)
+ *   A row without stored elements gives a dq row of +0.0, a column without stored elements dk and dv rows of +0.0; nnz == 0
+ *   writes +0.0 everywhere.  NaN and infinity follow from the arithmetic: a row whose forward row is NaN has a NaN dq row and
+ *   hands NaN to the dk and dv rows of its columns.
+ *   group (row pass) and col_group (column pass): lanes that own one short row or column, 8 | 16 | 32 | 64.  short_max
+ *   (0 .. 64): rows / columns of at most short_max elements take the sub-group form, longer ones up to `chunk` a wave each,
+ *   longer ones pieces through the workspace (launches that each end before the next reads their results: no workgroup
+ *   waits for another).  chunk: a multiple of 64 in 64 .. 1024.  max_row / max_col: the longest row / column, 0 .. nnz; they
+ *   only decide which launches are made.
+ *   ws: spamd_attention_grad_ws_bytes(val_dtype, nnz, H, D, Dv, chunk) bytes, needed whenever nnz > 0 (SPAMD_EWS): p_i and
+ *   y_i per stored element and head - written once by the row pass, read once by the column pass -, and for nnz > chunk the
+ *   piece forms' statistics and piece outputs.  The arrays are trusted: s_ptr and c_ptr ascend from 0 to nnz, s_idx < N,
+ *   c_row < M, c_perm is a permutation of 0 .. nnz-1.
+ *   Returns before any launch: SPAMD_ETYPE for other type codes; SPAMD_EINVAL for negative sizes, pitches or strides,
+ *   max_row or max_col above nnz, group / col_group / short_max / chunk outside the above, or null pointers with work to
+ *   do; SPAMD_EWS; 0 when H == 0 or dq, dk and dv are all empty.
+ * ------------------------------------------------------------------------------------- */
+int64_t spamd_attention_grad_ws_bytes(int val_dtype, int64_t nnz, int64_t H, int64_t D, int64_t Dv, int64_t chunk);
+int spamd_attention_grad(int val_dtype, int idx_dtype, int64_t M, int64_t N, int64_t nnz, int64_t H, int64_t D, int64_t Dv,
+                         const void* s_ptr, const void* s_idx, const void* s_val, const void* c_ptr, const int64_t* c_perm,
+                         const void* c_row, const void* q, int64_t q_pitch, int64_t q_head, const void* k, int64_t k_pitch,
+                         int64_t k_head, const void* v, int64_t v_pitch, int64_t v_head, const void* g, int64_t g_pitch,
+                         int64_t g_head, int has_scale, double scale, int group, int col_group, int64_t short_max,
+                         int64_t chunk, int64_t max_row, int64_t max_col, void* ws, int64_t ws_bytes, void* dq, void* dk,
+                         void* dv, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -103,3 +103,110 @@ def sparse_attention(s, q, k, v, *, scale=None):
     dq, dk, dv = (dev.to_device(t, s.device) for t in (q, k, v))
     out = K.attention_rows(indptr, indices, K.convert(data, dt), dq, dk, dv, max_len, scale=scale)
     return out if torch_out else dev.to_numpy(out)
+
+
+# ---- the backward pass (csrc/attention_grad.hip) -------------------------------------------------------------------------------------
+def _build_grad_plan(indices, indptr, shape):
+    """the column grouping of a CSR pattern, from the key and index primitives: (colptr [N + 1] and colrows [nnz] at the width of
+    `indptr`, colperm int64[nnz], the longest column).  The sort is stable, so a column's elements keep their stored order"""
+    from ._reduce import _scalar_dev
+    from ._softmax import _max_len
+    from ._umath import binary_arrays
+
+    M, N = int(shape[0]), int(shape[1])
+    dev_ = indices.device
+    rows = binary_arrays("floor_divide_i64", K.csr_to_keys(indptr, indices, M, N), _scalar_dev(N, torch.int64, dev_), b_scalar=True)
+    cols, colperm = K.sort_keys(K.convert(indices, torch.int64), max(N - 1, 1))
+    colptr = K.rows_to_indptr(cols, N)
+    max_col = _max_len(colptr)
+    colrows = K.gather(rows, colperm)
+    return K.convert(colptr, indptr.dtype), colperm, K.convert(colrows, indptr.dtype), max_col
+
+
+def _column_grouping(s, indices, indptr):
+    """`_build_grad_plan` of the mask, kept on the array under a stamp of its index buffers as `_attention_plan` is"""
+    from ._softmax import _coord_stamp, _stamp_holds
+
+    stamp = _coord_stamp(s)
+    plan = s.__dict__.get("_attention_grad_plan")
+    if plan is None or not _stamp_holds(plan["stamp"], stamp) or plan["indptr"] is not indptr:
+        colptr, colperm, colrows, max_col = _build_grad_plan(indices, indptr, s.shape)
+        plan = s.__dict__["_attention_grad_plan"] = {"stamp": stamp, "indptr": indptr, "colptr": colptr, "colperm": colperm,
+                                                     "colrows": colrows, "max_col": max_col}
+    else:
+        plan["stamp"].update(stamp)
+    return plan
+
+
+def sparse_attention_grad(s, q, k, v, grad, *, scale=None):
+    """The gradient of `sparse_attention(s, q, k, v, scale=scale)`: `(dq, dk, dv)` for `grad`, the gradient of its result, in
+    one fused backward pass (two passes over the mask, no atomics).
+
+    `s`, `q`, `k`, `v` and `scale` are those of `sparse_attention`: the same masks, operand kinds, strides, head axes and
+    errors.  `grad` (..., M, Dv): a NumPy array or torch tensor of the operands' type and head axes (any strides).  Returns
+    `dq` (..., M, D), `dk` (..., N, D) and `dv` (..., N, Dv): ndarrays if all four operands are ndarrays, else torch device
+    tensors.  The gradient with respect to the mask values is not computed.
+
+    A row without stored elements has a `dq` row of +0.0, a column without stored elements `dk` and `dv` rows of +0.0.  A
+    row whose forward row is NaN has a NaN `dq` row and hands NaN to the `dk` / `dv` rows of its columns.
+
+    The order of every operation is fixed (include/sparse_amd.h, A16): the probabilities are recomputed with the forward's
+    bits, `dk` and `dv` sum each column's stored elements in stored order - the same bits on every call.  The column grouping
+    of the mask is pattern-only state, built once and kept on the array; a second call converts and builds nothing."""
+    from ._softmax import _check_arguments
+    from ._utils import check_zero_fill_value
+
+    if not isinstance(s, (COO, GCXS)):
+        raise TypeError(f"sparse_attention needs a COO or GCXS mask, got {type(s).__name__}")
+    if s.ndim != 2:
+        raise ValueError(f"sparse_attention needs a 2-D mask, `s` has {s.ndim} dimensions (every head shares one 2-D mask)")
+    _check_arguments(s.dtype, 2, -1, scale)
+    check_zero_fill_value(s)
+    dt, lead = _check_operands(s.shape, q, k, v)
+    if not isinstance(grad, (np.ndarray, torch.Tensor)):
+        raise TypeError(f"sparse_attention_grad: `grad` must be a NumPy array or a torch tensor, got {type(grad).__name__}")
+    gdt = grad.dtype if isinstance(grad, torch.Tensor) else _NP_OPERAND.get(grad.dtype, grad.dtype)
+    if gdt != dt:
+        raise TypeError(f"sparse_attention_grad: `grad` must have the type of q, k and v ({dt}), got {gdt}")
+    M, N, D, Dv = int(s.shape[0]), int(s.shape[1]), int(q.shape[-1]), int(v.shape[-1])
+    if tuple(int(n) for n in grad.shape) != lead + (M, Dv):
+        raise ValueError(f"shape-mismatch for sparse_attention_grad: `grad` {tuple(grad.shape)} is not the shape of the forward's "
+                         f"result {lead + (M, Dv)}")
+    torch_out = any(isinstance(t, torch.Tensor) for t in (q, k, v, grad))
+    if s.nnz == 0 or 0 in lead:
+        outs = tuple(torch.zeros(lead + shp, dtype=dt, device=s.device) for shp in ((M, D), (N, D), (N, Dv)))
+    else:
+        data, indices, indptr = _csr_of_mask(s)
+        max_row = _longest_row(s, indptr)
+        plan = _column_grouping(s, indices, indptr)
+        tq, tk, tv, tg = (dev.to_device(t, s.device) for t in (q, k, v, grad))
+        outs = K.attention_grad_rows(indptr, indices, K.convert(data, dt), plan["colptr"], plan["colperm"], plan["colrows"], tq, tk,
+                                     tv, tg, max_row, plan["max_col"], scale=scale)
+    return outs if torch_out else tuple(dev.to_numpy(t) for t in outs)
+
+
+class _SparseAttention(torch.autograd.Function):
+    """forward: the fused call of `sparse_attention`; backward: `sparse_attention_grad` (no gradient for the mask or the scale)"""
+
+    @staticmethod
+    def forward(ctx, s, scale, q, k, v):
+        ctx.s, ctx.scale = s, scale
+        ctx.save_for_backward(q, k, v)
+        return sparse_attention(s, q.detach(), k.detach(), v.detach(), scale=scale)
+
+    @staticmethod
+    def backward(ctx, grad):
+        q, k, v = ctx.saved_tensors
+        dq, dk, dv = sparse_attention_grad(ctx.s, q, k, v, grad, scale=ctx.scale)
+        need = ctx.needs_input_grad
+        return None, None, dq if need[2] else None, dk if need[3] else None, dv if need[4] else None
+
+
+def sparse_attention_autograd(s, q, k, v, *, scale=None):
+    """`sparse_attention(s, q, k, v, scale=scale)` as a differentiable torch function: the forward is that fused call - the
+    same bits -, the backward is `sparse_attention_grad`.  `q`, `k` and `v` are torch tensors; the mask `s` and `scale` get
+    no gradient, and an operand that does not require one gets None."""
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"sparse_attention_autograd: `{name}` must be a torch tensor, got {type(t).__name__}")
+    return _SparseAttention.apply(s, scale, q, k, v)

@@ -1794,6 +1794,90 @@ def attention_rows(indptr, indices, svals, q, k, v, max_len, *, scale=None, grou
 
 
 # ---------------------------------------------------------------------------------------------
+# the backward pass of sparse attention (csrc/attention_grad.hip)
+# ---------------------------------------------------------------------------------------------
+# The chunk of the backward pass is part of its order contract for rows AND columns longer than it (include/sparse_amd.h A16) and
+# must be the forward's for the probabilities to carry the forward's bits: it IS `ATTENTION_CHUNK` (`attention_grad_chunk`).  The
+# widths and ATTENTION_GRAD_SHORT_MAX never change a bit.  Chosen with tools/attention_grad_time.py --sweep (MI355X, float32, ms
+# per call of `attention_grad_rows`, median of 5 rounds of 20 calls, spread below 1 %), one parameter at a time around 16 / 16 /
+# 64 / 1024: (a) CSR graph of 2^17 nodes, mean degree 32, D = Dv = 64; (b) the same graph, 8 heads of D = Dv = 16; (c) one hub row
+# of 10^6 among 2^16 rows of 8, D = Dv = 64; (c') its transpose, one hub column:
+#   group (row pass)   8       16      32      64
+#     (a)            0.920   0.901   0.950   1.275     16 is the forward's width, and the narrowest that parks no scalar in a
+#     (b)            5.180   5.128   6.066   8.634     vector lane (DESIGN A16, resource table)
+#   col_group          8       16      32      64
+#     (a)            0.914   0.900   0.890   0.879     the column pass only gathers: wider sub-groups hold fewer accumulators a
+#     (b)            5.196   5.133   4.994   5.088     lane; 32 is the best at (b) and within 1.3 % of the best at (a)
+#     (c)            2.292   2.295   2.379   2.611     (10^6 columns of one or two elements: reported only)
+#   short_max          0       16      32      64      (0 = every row and column a whole wave)
+#     (a)            2.784   2.808   2.192   0.901
+#     (b)           12.566  12.622  10.110   5.131
+#   chunk              64      128     256     512     1024
+#     (c)            9.87    5.40    3.17    2.31    2.29
+#     (c')          14.34    7.04    4.28    2.79    2.57
+ATTENTION_GRAD_SHORT_MAX = 64
+ATTENTION_GRAD_GROUP = 16
+ATTENTION_GRAD_COL_GROUP = 32
+
+
+def attention_grad_chunk():
+    return ATTENTION_CHUNK
+
+
+def attention_grad_rows(indptr, indices, svals, colptr, colperm, colrows, q, k, v, g, max_row, max_col, *, scale=None, group=None,
+                        col_group=None, chunk=None, form=None, short_max=None):
+    """(dq, dk, dv) of `attention_rows` for the gradient `g` [..., M, Dv] of its result (spamd_attention_grad).  The mask and
+    q, k, v are as there; `colptr` (N + 1, the type of `indptr`), `colperm` (int64[nnz]) and `colrows` (nnz, the type of
+    `indptr`) are the column grouping: the stored positions of every column in stored order and their row ids; `max_row` and
+    `max_col` the longest row and column.  `form` forces a kernel form on BOTH passes, for tests and sweeps: "short"
+    (sub-groups of `group` / `col_group` lanes; at most 64 elements a row and a column), "wide" (a wave each; at most `chunk`),
+    "long" (a wave up to `chunk`, default 64 here, pieces beyond); `short_max` moves the length at which a row or column goes
+    from a sub-group to a wave (sweeps)."""
+    dev = require_hip(indptr, indices, svals, colptr, colperm, colrows, q, k, v, g)
+    dt = svals.dtype
+    if dt not in (torch.float32, torch.float64) or any(t.dtype != dt for t in (q, k, v, g)):
+        raise TypeError("attention_grad: the mask values, q, k, v and g must all be float32 or all float64")
+    if not index_dtype_ok(indptr) or any(t.dtype != indptr.dtype for t in (indices, colptr, colrows)) or colperm.dtype != torch.int64:
+        raise TypeError("attention_grad: indptr, indices, colptr and colrows must all be int32 or all int64, colperm int64")
+    lead = tuple(q.shape[:-2])
+    if any(tuple(t.shape[:-2]) != lead for t in (k, v, g)):
+        raise ValueError("attention_grad: q, k, v and g must have the same leading axes")
+    M, D, N, Dv = int(q.shape[-2]), int(q.shape[-1]), int(k.shape[-2]), int(v.shape[-1])
+    nnz, max_row, max_col = int(svals.numel()), int(max_row), int(max_col)
+    if int(k.shape[-1]) != D or int(v.shape[-2]) != N or int(indptr.numel()) != M + 1 or tuple(g.shape[-2:]) != (M, Dv) \
+            or int(colptr.numel()) != N + 1 or int(colperm.numel()) != nnz or int(colrows.numel()) != nnz:
+        raise ValueError("attention_grad: shape mismatch between the mask, the column grouping, q, k, v and g")
+    if form not in (None,) + ATTENTION_FORMS:
+        raise ValueError(f"attention_grad: form must be one of {ATTENTION_FORMS} or None, got {form!r}")
+    chunk = (64 if form == "long" else attention_grad_chunk()) if chunk is None else int(chunk)
+    short_max = (ATTENTION_GRAD_SHORT_MAX if short_max is None else int(short_max)) if form in (None, "short") else 0
+    longest = max(max_row, max_col)
+    if form == "short" and longest > 64 or form == "wide" and longest > chunk:
+        raise ValueError(f"attention_grad: form {form!r} does not take a row or column of {longest} elements")
+    group = ATTENTION_GRAD_GROUP if group is None else int(group)
+    col_group = ATTENTION_GRAD_COL_GROUP if col_group is None else int(col_group)
+    q3, qp, qh = _rows3(q, dev)
+    k3, kp, kh = _rows3(k, dev)
+    v3, vp, vh = _rows3(v, dev)
+    g3, gp, gh = _rows3(g, dev)
+    H = int(q3.shape[0])
+    dq = torch.empty(lead + (M, D), dtype=dt, device=dev)
+    dk = torch.empty(lead + (N, D), dtype=dt, device=dev)
+    dv = torch.empty(lead + (N, Dv), dtype=dt, device=dev)
+    ws_bytes = int(_ffi.lib().spamd_attention_grad_ws_bytes(code_of(dt), nnz, H, D, Dv, chunk))
+    if ws_bytes < 0:
+        raise _ffi.HipBackendError(f"spamd_attention_grad_ws_bytes failed: {ws_bytes}")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    has_scale = scale is not None
+    sc = float(np.asarray(scale).astype(np_dtype(dt))) if has_scale else 0.0
+    _ffi.call("spamd_attention_grad", code_of(dt), code_of(indptr.dtype), M, N, nnz, H, D, Dv, ptr(indptr.contiguous()),
+              ptr(indices.contiguous()), ptr(svals.contiguous()), ptr(colptr.contiguous()), ptr(colperm.contiguous()),
+              ptr(colrows.contiguous()), ptr(q3), qp, qh, ptr(k3), kp, kh, ptr(v3), vp, vh, ptr(g3), gp, gh, int(has_scale), sc,
+              group, col_group, short_max, chunk, max_row, max_col, ptr(ws), ws_bytes, ptr(dq), ptr(dk), ptr(dv), stream_ptr(dev))
+    return dq, dk, dv
+
+
+# ---------------------------------------------------------------------------------------------
 # masked SpGEMM (csrc/masked_spgemm.hip)
 # ---------------------------------------------------------------------------------------------
 MASKED_DTYPES = (torch.float32, torch.float64, torch.int32, torch.int64)

@@ -1,0 +1,100 @@
+"""Seeded fuzz of sparse_amd.sparse_attention_grad (csrc/attention_grad.hip) against the NumPy restatement of its contract, bit
+for bit:
+
+    python tools/fuzz_attention_grad.py [--cases 40] [--seed 0] [--max-nnz 6000]
+
+A case draws: float32 | float64 operands, 32- | 64-bit indices, a chunk of 64 .. 1024, a sub-group width for each pass, uniform
+or Zipf lengths of up to 3000 - as the ROW lengths of the mask or, transposed, as its COLUMN lengths (hubs beyond the chunk
+among many short ones) -, a share of empty rows or columns, D and Dv of 1 .. 140, no head axis, three heads or 2 x 2, float,
+integer or boolean mask values, now and then a scale, a stored zero, an infinity or a NaN among the mask values - and the mask
+as a COO, a COO built unsorted, a CSR or a CSC; the operands as NumPy arrays, device tensors or row-strided device views.
+Prints one line per case; exits 1 at the first difference."""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import attention_cases as ac  # noqa: E402
+import attention_grad_cases as gc  # noqa: E402
+import softmax_cases as sc  # noqa: E402
+import sparse_amd  # noqa: E402
+from sparse_amd import _kernels as K  # noqa: E402
+
+
+def lengths_of(rng, max_nnz):
+    count = int(rng.integers(1, 120))
+    if rng.random() < 0.5:
+        n = rng.integers(0, int(rng.choice([4, 40, 200, 1500, 3000])) + 1, count)
+    else:
+        n = np.minimum(rng.zipf(float(rng.choice([1.2, 1.6, 2.5])), count), min(max_nnz // 2, 3000))
+    n[rng.random(count) < rng.choice([0.0, 0.3])] = 0
+    while n.sum() > max_nnz:
+        n[np.argmax(n)] //= 2
+    return [int(v) for v in n]
+
+
+def strided(x):
+    w = torch.zeros(x.shape[:-1] + (x.shape[-1] + 5,), dtype=x.dtype, device=x.device)
+    w[..., 2:2 + x.shape[-1]] = x
+    return w[..., 2:2 + x.shape[-1]]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cases", type=int, default=40)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--max-nnz", type=int, default=6000)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("fuzz_attention_grad.py runs the kernels: no HIP device visible")
+    for case in range(a.cases):
+        rng = np.random.default_rng([a.seed, case])
+        dtype = rng.choice([np.float32, np.float64])
+        idx = rng.choice([np.int32, np.int64])
+        mdt = rng.choice([dtype, dtype, np.int32, np.int64, np.bool_])
+        chunk = K.ATTENTION_CHUNK = int(rng.choice([64, 128, 192, 512, 1024]))
+        group = K.ATTENTION_GRAD_GROUP = int(rng.choice(K.ATTENTION_GROUPS))
+        col_group = K.ATTENTION_GRAD_COL_GROUP = int(rng.choice(K.ATTENTION_GROUPS))
+        lengths = lengths_of(rng, a.max_nnz)
+        along = rng.choice(["rows", "columns"])
+        D, Dv = (int(rng.choice([1, 3, 16, 17, 63, 64, 65, 128, 140])) for _ in range(2))
+        lead = [(), (), (3,), (2, 2)][int(rng.integers(4))]
+        seed = int(rng.integers(1 << 30))
+        indptr, indices, vals, shape = gc.transposed_mask(seed, lengths, mdt) if along == "columns" else ac.csr_mask(seed, lengths, mdt)
+        if len(vals) and np.dtype(mdt).kind == "f" and rng.random() < 0.3:
+            vals[rng.integers(0, len(vals), 3)] = rng.choice([np.inf, -np.inf, np.nan, 0.0, -0.0], 3)
+        q, k, v = ac.operands(int(rng.integers(1 << 30)), shape, D, Dv, dtype, lead=lead, spread=float(rng.choice([1, 8])))
+        g = gc.grad_operand(int(rng.integers(1 << 30)), shape, Dv, dtype, lead=lead)
+        scale = float(rng.choice([-2.0, 0.125, 3.0])) if rng.random() < 0.4 else None
+        layout = rng.choice(["coo", "unsorted", "csr", "csc"])
+        coords = ac.coords_of(indptr, indices).astype(idx)
+        if layout == "unsorted":
+            perm = rng.permutation(len(vals))
+            s = sparse_amd.COO(coords[:, perm], vals[perm], shape=shape, idx_dtype=idx, device="cuda:0")
+        else:
+            s = sparse_amd.COO(coords, vals, shape=shape, has_duplicates=False, sorted=True, idx_dtype=idx, device="cuda:0")
+            if layout in ("csr", "csc"):
+                s = s.asformat("gcxs", compressed_axes=(0,) if layout == "csr" else (1,))
+        how = rng.choice(["numpy", "torch", "strided"])
+        ops = (q, k, v, g) if how == "numpy" else tuple(torch.from_numpy(x).to("cuda:0") for x in (q, k, v, g))
+        if how == "strided":
+            ops = tuple(strided(x) for x in ops)
+        outs = sparse_amd.sparse_attention_grad(s, *ops, scale=scale)
+        outs = [o if isinstance(o, np.ndarray) else o.cpu().numpy() for o in outs]
+        want = gc.grad_heads(indptr, indices, vals, q, k, v, g, chunk, scale)
+        ok = all(sc.same_bits(o, w) for o, w in zip(outs, want))
+        longest_col = int(np.bincount(np.asarray(indices, dtype=np.int64), minlength=1).max()) if len(vals) else 0
+        print(f"case {case}: {np.dtype(dtype)} mask {np.dtype(mdt)} {np.dtype(idx)} {layout} {how} chunk {chunk} groups {group}/{col_group} "
+              f"scale {scale} D {D} Dv {Dv} heads {lead} shape {shape} nnz {len(vals)} longest row {int(np.diff(indptr).max())} "
+              f"column {longest_col}: {'same bits' if ok else 'DIFFERENT'}", flush=True)
+        if not ok:
+            raise SystemExit(1)
+
+
+if __name__ == "__main__":
+    main()
