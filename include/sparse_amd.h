@@ -492,7 +492,9 @@ int spamd_hot_rows_combine(int val_dtype, int64_t n_hot, int64_t n_cols, const v
  *                              (sparse/numba_backend/_common.py:543-570,639-717,907-976)
  *   Expand-sort-compress: the two entry points below produce, for the A elements [p0, p0+np),
  *   (1) cnt[i] = nnz of B row a_indices[p0+i]; after the caller's exclusive scan (offsets, P):
- *   (2) keys[t] = a_rows[p]*n_col + b_col, vals[t] = a*b for every product t in [0, P).
+ *   (2) keys[t] = a_rows[p]*n_col + b_col, vals[t] = 0 + a*b for every product t in [0, P): the reference's accumulator
+ *   starts at +0, so a product of -0.0 enters it as +0.0 (every other value, and every integer, is a*b as it is).  The
+ *   row-local, small and bitmap kernels below take their products the same way.
  *   A stable sort by key + spamd_segment_reduce(add) then gives every output element summed in
  *   the reference's order (bit-identical), with rows sorted by column.
  *   val_dtype of (2): F32 | F64 | I32 | I64 | C64 | C128; a complex product is the four rounded products, the rounded

@@ -127,6 +127,18 @@ __host__ __device__ __forceinline__ Cplx<R> operator+(Cplx<R> a, Cplx<R> b) {
   return Cplx<R>{a.re + b.re, a.im + b.im};
 }
 
+// A product p of sparse x sparse as it enters the reference's zeroed accumulator (`sums = zeros`, `sums[j] += a * b`): 0 + p.
+// That differs from p for p = -0.0 alone (-> +0.0; every component of a complex p) and leaves integers as they are.  With it
+// no partial sum is ever -0.0, so every later `acc + p'` has the reference's bits whether the kernel starts a sum from zero
+// or from its first product, and in whatever order a re-associating reduce adds: an output element whose products are all
+// -0.0 comes out +0.0, as the reference's does, and the bit-wise prune drops it.
+template <typename T>
+__host__ __device__ __forceinline__ T from_zero_sum(T p) {
+#pragma clang fp contract(off)
+  if constexpr (std::is_integral<T>::value) return p;
+  else return T{} + p;
+}
+
 template <typename T, int N>
 struct alignas(sizeof(T) * N) Vec {
   T v[N];

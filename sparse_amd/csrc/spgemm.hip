@@ -54,7 +54,7 @@ __global__ void __launch_bounds__(256) spgemm_expand_kernel(
     const int64_t p = p0 + lo;
     const int64_t q = (int64_t)b_ptr[(int64_t)a_idx[p]] + (t - offs[lo]);
     keys[t] = a_rows[p] * n_col + (int64_t)b_idx[q];
-    vals[t] = a_data[p] * b_data[q];
+    vals[t] = from_zero_sum(a_data[p] * b_data[q]);   // (0 + p: a lone -0.0 product is the reference's +0.0)
   }
 }
 

@@ -503,7 +503,7 @@ spgemm_bitmap_kernel(int64_t n_vrow, int np_arg, int64_t range, int ngroups, con
           if (slot < DUP) {
             dup[slot].key = (c << 8) | e;
             dup[slot].rank = BMK_NONE;
-            dup[slot].val = sc->aval[e] * bvN[j];
+            dup[slot].val = from_zero_sum(sc->aval[e] * bvN[j]);
           }
         } else {
           first_mask |= 1u << j;
@@ -571,7 +571,7 @@ spgemm_bitmap_kernel(int64_t n_vrow, int np_arg, int64_t range, int ngroups, con
           if (slot < DUP) {
             dup[slot].key = (c << 8) | e;
             dup[slot].rank = (unsigned)r;
-            dup[slot].val = sc->aval[e] * bvN[j];
+            dup[slot].val = from_zero_sum(sc->aval[e] * bvN[j]);
           }
         }
       }
@@ -586,7 +586,7 @@ spgemm_bitmap_kernel(int64_t n_vrow, int np_arg, int64_t range, int ngroups, con
     for (int j = 0; j < ITEMS; ++j) {
       if ((first_mask >> j) & 1u) {
         const unsigned e = (eN[j / 4] >> (8 * (j % 4))) & 255u;
-        put((rk[j / 2] >> (16 * (j % 2))) & 0xffffu, colN[j], sc->aval[e] * bvN[j]);
+        put((rk[j / 2] >> (16 * (j % 2))) & 0xffffu, colN[j], from_zero_sum(sc->aval[e] * bvN[j]));
       }
     }
     BMK_T(8)

@@ -258,6 +258,10 @@ spgemm_rowrank_kernel(int64_t n_col, int col_bits, int ebits, const I* __restric
       if (e <= cn) prefix[e] = before;
       before += len[j];
     }
+    // The threads above write the entries e < BLOCK * EPT, which is STAGE for most classes: the end of a FULL chunk,
+    // prefix[STAGE], is written here.  The walk `while (prefix[e + 1] <= p)` below reads it when the chunk's last element has
+    // products; left to whatever LDS held, it would send the walk past the chunk, to garbage offsets into B.
+    if (tid == 0) prefix[cn] = chunk_total;
     __syncthreads();
     // Product p of the ROW belongs to thread p % BLOCK (item p / BLOCK): for one item index, consecutive lanes read
     // consecutive entries of a B row — a wave-load touches two or three lines instead of 64 (with p / ITEMS = thread, every
@@ -291,7 +295,7 @@ spgemm_rowrank_kernel(int64_t n_col, int col_bits, int ebits, const I* __restric
         for (int g = 0; g < G; ++g) {
           if (j0 + g < ITEMS && on[g]) {
             keys[j0 + g] = ((KEY)(unsigned)b_idx[q[g]] << ebits) | (KEY)(unsigned)ee[g];
-            vals[j0 + g] = av[g] * b_val[q[g]];
+            vals[j0 + g] = from_zero_sum(av[g] * b_val[q[g]]);   // (0 + p: the rank below starts a run with its first product)
           }
         }
       }

@@ -91,7 +91,7 @@ spgemm_small_kernel(int64_t n_row, int n_col, int words, const I* __restrict__ a
         if (c <= cp || c >= n_col) {
           bad = true;
         } else {
-          const V p = sm_mul(av, b_val[j]);
+          const V p = from_zero_sum(sm_mul(av, b_val[j]));   // (0 + p: the first product of a column is stored as it is)
           const unsigned bit = 1u << (c & 31);
           const unsigned old = atomicOr(&bm[c >> 5], bit);
           acc[c] = (old & bit) ? sm_add(acc[c], p) : p;

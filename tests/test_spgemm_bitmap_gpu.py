@@ -333,3 +333,23 @@ def test_b_rows_holding_a_column_twice_fail_over_to_the_bucket_kernels(split):
     sel = gi % 1000 == 0
     np.add.at(dense, (rows[sel], gi[sel] // 1000), gd[sel])
     assert np.allclose(dense, want, rtol=1e-12, atol=1e-12)
+
+
+@pytest.mark.parametrize("split", [False, "first"])
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_signed_zeros_of_the_bitmap_forms(split, dtype):
+    """the `zeros` pool of tests/spgemm_cases.py through the wide and the split form: a lone -0.0 product (0 * -2, an
+    underflow), a run of them, x - x, inf * 0 and a stored -0.0 operand give what the reference's `sums = zeros`,
+    `sums[j] += a * b` gives - +0.0 wherever every product is a zero, bit for bit, never -0.0"""
+    import spgemm_cases as sc
+
+    n = 1_000_000                 # (within the wide form's columns for 8-byte values too)
+    st = sc.zeros_struct(n, 3)
+    A, B = sc.operands(st, "zeros", np.dtype(dtype).name)
+    got, stats = _run_forms((st.n_row, n), A, B, split)
+    assert stats.get("kernel") == "bitmap" and (stats.get("parts", 1) > 1) == (split == "first"), stats
+    data, indices, indptr = sc.spgemm_ref(st.n_row, n, A, B)
+    gd, gi, gp = (t.cpu().numpy() for t in got)
+    assert np.array_equal(gp, indptr) and np.array_equal(gi, indices)
+    assert gd.dtype == data.dtype and np.array_equal(sc.bits_of(gd), sc.bits_of(data))
+    assert not ((gd == 0) & np.signbit(gd)).any() and (sc.bits_of(gd) == 0).sum() >= 6
