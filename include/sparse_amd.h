@@ -873,6 +873,16 @@ int spamd_softmax(int val_dtype, int idx_dtype, int64_t nseg, int64_t nnz, const
  *   Returns before any launch: SPAMD_ETYPE for other type codes; SPAMD_EINVAL for negative sizes, pitches or strides,
  *   max_len > nnz, group / short_max / chunk outside the above, or null pointers with work to do; 0 for M == 0, H == 0 or
  *   Dv == 0.  nnz == 0 writes +0.0 everywhere.
+ *   spamd_attention_bias: the same with an additive bias per stored element and head (an edge encoding, a relative-position
+ *   bias, a per-head mask).  bias (val_dtype) is read at the stored (CSR) position: element i of row r of head h, at the
+ *   position pos = s_ptr[r] + i, takes b_i = bias[h * bias_head + pos] (elements; bias_head == 0: every head shares one bias of
+ *   nnz values).  One step follows the two of t_i:
+ *     t_i   = t_i + b_i, one add, rounded once, after the scale
+ *   and p_i and out follow from these t_i exactly as above.  The rest is arithmetic: a bias of -inf gives p_i = +0.0 (a mask
+ *   of that head's own), a row whose t_i are all -inf or hold a NaN or +inf is NaN; a bias of +0.0 everywhere gives the bits of
+ *   spamd_attention; in a row of at most `chunk` elements a bias of -inf on the trailing elements gives the bits of the mask
+ *   without them (fma(+0.0, v, acc) = acc for finite v).  bias == NULL is spamd_attention itself, bit for bit; bias_head < 0 is
+ *   SPAMD_EINVAL.  The workspace is spamd_attention_ws_bytes: the long form parks the biased scores.
  * ------------------------------------------------------------------------------------- */
 int64_t spamd_attention_ws_bytes(int val_dtype, int64_t nnz, int64_t H, int64_t Dv, int64_t chunk);
 int spamd_attention(int val_dtype, int idx_dtype, int64_t M, int64_t N, int64_t nnz, int64_t H, int64_t D, int64_t Dv,
@@ -880,9 +890,14 @@ int spamd_attention(int val_dtype, int idx_dtype, int64_t M, int64_t N, int64_t 
                     const void* k, int64_t k_pitch, int64_t k_head, const void* v, int64_t v_pitch, int64_t v_head,
                     int has_scale, double scale, int group, int64_t short_max, int64_t chunk, int64_t max_len, void* ws,
                     int64_t ws_bytes, void* out, void* stream);
+int spamd_attention_bias(int val_dtype, int idx_dtype, int64_t M, int64_t N, int64_t nnz, int64_t H, int64_t D, int64_t Dv,
+                         const void* s_ptr, const void* s_idx, const void* s_val, const void* q, int64_t q_pitch, int64_t q_head,
+                         const void* k, int64_t k_pitch, int64_t k_head, const void* v, int64_t v_pitch, int64_t v_head,
+                         int has_scale, double scale, int group, int64_t short_max, int64_t chunk, int64_t max_len,
+                         const void* bias, int64_t bias_head, void* ws, int64_t ws_bytes, void* out, void* stream);
 
 /* =======================================================================================
- * A16  the backward pass of sparse attention (csrc/attention_grad.hip): from g = d loss / d out (H, M, Dv) of A15, for every
+ * A16 the backward pass of sparse attention (csrc/attention_grad.hip): from g = d loss / d out (H, M, Dv) of A15, for every
  *   head, dq (H, M, D), dk (H, N, D) and dv (H, N, Dv).  The gradient with respect to the mask values is not computed.
  *   The mask, q, k, v, has_scale and scale are A15's.  g has its own row pitch and head stride, last axis contiguous.  The
  *   column grouping is state of the pattern alone, built by the caller: c_ptr (idx_dtype, N + 1 entries ascending from 0 to
@@ -922,6 +937,15 @@ int spamd_attention(int val_dtype, int idx_dtype, int64_t M, int64_t N, int64_t 
  *   Returns before any launch: SPAMD_ETYPE for other type codes; SPAMD_EINVAL for negative sizes, pitches or strides,
  *   max_row or max_col above nnz, group / col_group / short_max / chunk outside the above, or null pointers with work to
  *   do; SPAMD_EWS; 0 when H == 0 or dq, dk and dv are all empty.
+ *   spamd_attention_grad_bias: the backward pass of spamd_attention_bias.  bias and bias_head are as there; t_i and p_i are
+ *   recomputed with the bias, the same bits as the forward's; e_i, u_i, delta, z_i, y_i, dq, dk and dv are as above.  One
+ *   more output, the gradient with respect to the bias:
+ *     dbias[h][pos] = z_i
+ *   dbias is (H, nnz) contiguous of val_dtype, always per head (a shared bias's gradient is the caller's sum over h); every
+ *   element is written exactly once, by the row pass in each of its three forms, without an atomic: it is as reproducible and
+ *   as independent of group / col_group / short_max / max_row / max_col as dq.  dbias == NULL skips the store.  bias == NULL
+ *   is spamd_attention_grad itself, bit for bit, and dbias is then not written; bias_head < 0 is SPAMD_EINVAL.  The
+ *   workspace is spamd_attention_grad_ws_bytes.
  * ------------------------------------------------------------------------------------- */
 int64_t spamd_attention_grad_ws_bytes(int val_dtype, int64_t nnz, int64_t H, int64_t D, int64_t Dv, int64_t chunk);
 int spamd_attention_grad(int val_dtype, int idx_dtype, int64_t M, int64_t N, int64_t nnz, int64_t H, int64_t D, int64_t Dv,
@@ -931,6 +955,13 @@ int spamd_attention_grad(int val_dtype, int idx_dtype, int64_t M, int64_t N, int
                          int64_t g_head, int has_scale, double scale, int group, int col_group, int64_t short_max,
                          int64_t chunk, int64_t max_row, int64_t max_col, void* ws, int64_t ws_bytes, void* dq, void* dk,
                          void* dv, void* stream);
+int spamd_attention_grad_bias(int val_dtype, int idx_dtype, int64_t M, int64_t N, int64_t nnz, int64_t H, int64_t D, int64_t Dv,
+                              const void* s_ptr, const void* s_idx, const void* s_val, const void* c_ptr, const int64_t* c_perm,
+                              const void* c_row, const void* q, int64_t q_pitch, int64_t q_head, const void* k, int64_t k_pitch,
+                              int64_t k_head, const void* v, int64_t v_pitch, int64_t v_head, const void* g, int64_t g_pitch,
+                              int64_t g_head, int has_scale, double scale, int group, int col_group, int64_t short_max,
+                              int64_t chunk, int64_t max_row, int64_t max_col, const void* bias, int64_t bias_head, void* dbias,
+                              void* ws, int64_t ws_bytes, void* dq, void* dk, void* dv, void* stream);
 
 #ifdef __cplusplus
 }

@@ -41,6 +41,52 @@ def _check_operands(s_shape, q, k, v):
     return dts[0], lead
 
 
+def _check_bias(bias, dt, lead, nnz, what="sparse_attention"):
+    """the checks of a bias that need no device: kind, type (no silent conversion) and shape"""
+    if bias is None:
+        return
+    if not isinstance(bias, (np.ndarray, torch.Tensor)):
+        raise TypeError(f"{what}: `bias` must be a NumPy array or a torch tensor of one value per stored element of `s` (a sparse "
+                        f"or other array is not accepted), got {type(bias).__name__}")
+    bdt = bias.dtype if isinstance(bias, torch.Tensor) else _NP_OPERAND.get(bias.dtype, bias.dtype)
+    if bdt != dt:
+        raise TypeError(f"{what}: `bias` must have the type of q, k and v ({dt}; it is not converted), got {bdt}")
+    shape = tuple(int(n) for n in bias.shape)
+    if shape != (nnz,) and shape != lead + (nnz,):
+        raise ValueError(f"shape-mismatch for {what}: `bias` {shape} is neither ({nnz},) - one value per stored element, shared by "
+                         f"the heads - nor {lead + (nnz,)}")
+
+
+def _bias_order(s):
+    """None when the order of `s.data` - the caller's - is the CSR order the kernel reads (a COO, a row-compressed GCXS); for a
+    column-compressed GCXS the plan {"perm": CSR position -> caller's position, "inv": caller's position -> CSR position}: the
+    stable re-compression that makes the CSR twin, applied to the positions as data.  Pattern-only state, kept on the array
+    under a stamp of its index buffers as `_attention_plan` is"""
+    from ._softmax import _coord_stamp, _stamp_holds
+
+    if not (isinstance(s, GCXS) and s.compressed_axes != (0,)):
+        return None
+    stamp = _coord_stamp(s)
+    plan = s.__dict__.get("_attention_bias_perm")
+    if plan is None or not _stamp_holds(plan["stamp"], stamp):
+        pos = torch.arange(s.nnz, dtype=torch.int64, device=s.device)
+        perm = K._csc_to_csr(s.shape, pos, s.indices, s.indptr)[0]
+        plan = s.__dict__["_attention_bias_perm"] = {"stamp": stamp, "perm": perm, "inv": K.sort_keys(perm, max(s.nnz - 1, 1))[1]}
+    else:
+        plan["stamp"].update(stamp)
+    return plan
+
+
+def _bias_in_csr_order(s, bias):
+    """the bias on the mask's device in the order the kernel reads: untouched where that is the caller's order, else gathered
+    through the memoised permutation, once"""
+    b = dev.to_device(bias, s.device)
+    order = _bias_order(s)
+    if order is None:
+        return b
+    return K.gather(b.reshape(-1, s.nnz), order["perm"]).reshape(b.shape)
+
+
 def _csr_of_mask(s):
     """(data, indices, indptr) the kernel reads: a row-compressed GCXS's own arrays untouched, else the memoised CSR form"""
     from ._dot import _csr_triplet
@@ -64,14 +110,23 @@ def _longest_row(s, indptr):
     return plan["max_len"]
 
 
-def sparse_attention(s, q, k, v, *, scale=None):
-    """`softmax_over_stored(scale * (s * (q @ k.T))) @ v` for every head, in one fused kernel.
+def sparse_attention(s, q, k, v, *, scale=None, bias=None):
+    """`softmax_over_stored(scale * (s * (q @ k.T)) + bias) @ v` for every head, in one fused kernel.
 
     `s`: a 2-D COO or GCXS (either compressed axis) of shape (M, N) with a zero fill value; float32, float64, integer or
     boolean values, converted to the result type on the device; complex and 16-bit values raise TypeError.  `q` (..., M, D),
     `k` (..., N, D), `v` (..., N, Dv): NumPy arrays or torch tensors (any strides), all float32 or all float64 - the result
     type.  The leading axes are the heads: absent, or identical on all three (no broadcasting); every head uses the same
     mask.  `scale`: None or a real scalar, rounded to the result type once.
+
+    `bias`: None, or one additive value per stored element - an edge encoding, a relative-position bias -: a NumPy array or
+    torch tensor of the operands' type (it is not converted; any strides) of shape `(s.nnz,)`, shared by the heads, or
+    `lead + (s.nnz,)`, one per head.  It is aligned with the array the caller holds: element `i` belongs to `s.data[i]` - to
+    `s.coords[:, i]` of a COO, to `s.indices[i]` inside its compressed slice of a GCXS of either axis.  It is added to the
+    score after the scale, `t = scale * (s * (q . k)) + bias`, one add rounded once (A15), so a bias of +0.0 changes no bit.  A
+    bias of -inf gives that stored element the probability +0.0 in that head: per-head masks over one shared pattern (a row
+    of one head whose elements are all -inf is NaN, as below; trailing -inf elements of a row of at most `ATTENTION_CHUNK`
+    elements give the bits of the mask without them).  A sparse array or a dense (M, N) array is not accepted.
 
     Returns the dense (..., M, Dv) result: a torch device tensor if any of q, k, v was a torch tensor, else an ndarray.  An
     unstored position of `s` counts as minus infinity; a row without stored elements gives a row of +0.0, not NaN.  Stored
@@ -93,6 +148,7 @@ def sparse_attention(s, q, k, v, *, scale=None):
     _check_arguments(s.dtype, 2, -1, scale)
     check_zero_fill_value(s)
     dt, lead = _check_operands(s.shape, q, k, v)
+    _check_bias(bias, dt, lead, int(s.nnz))
     torch_out = any(isinstance(t, torch.Tensor) for t in (q, k, v))
     M, Dv = int(s.shape[0]), int(v.shape[-1])
     if s.nnz == 0 or M == 0 or Dv == 0 or 0 in lead:
@@ -101,7 +157,8 @@ def sparse_attention(s, q, k, v, *, scale=None):
     data, indices, indptr = _csr_of_mask(s)
     max_len = _longest_row(s, indptr)
     dq, dk, dv = (dev.to_device(t, s.device) for t in (q, k, v))
-    out = K.attention_rows(indptr, indices, K.convert(data, dt), dq, dk, dv, max_len, scale=scale)
+    db = None if bias is None else _bias_in_csr_order(s, bias)
+    out = K.attention_rows(indptr, indices, K.convert(data, dt), dq, dk, dv, max_len, scale=scale, bias=db)
     return out if torch_out else dev.to_numpy(out)
 
 
@@ -138,14 +195,20 @@ def _column_grouping(s, indices, indptr):
     return plan
 
 
-def sparse_attention_grad(s, q, k, v, grad, *, scale=None):
-    """The gradient of `sparse_attention(s, q, k, v, scale=scale)`: `(dq, dk, dv)` for `grad`, the gradient of its result, in
-    one fused backward pass (two passes over the mask, no atomics).
+def sparse_attention_grad(s, q, k, v, grad, *, scale=None, bias=None):
+    """The gradient of `sparse_attention(s, q, k, v, scale=scale, bias=bias)`: `(dq, dk, dv)` for `grad`, the gradient of its
+    result, in one fused backward pass (two passes over the mask, no atomics); with a `bias`, `(dq, dk, dv, dbias)`.
 
     `s`, `q`, `k`, `v` and `scale` are those of `sparse_attention`: the same masks, operand kinds, strides, head axes and
     errors.  `grad` (..., M, Dv): a NumPy array or torch tensor of the operands' type and head axes (any strides).  Returns
     `dq` (..., M, D), `dk` (..., N, D) and `dv` (..., N, Dv): ndarrays if all four operands are ndarrays, else torch device
     tensors.  The gradient with respect to the mask values is not computed.
+
+    `bias` is that of `sparse_attention`: the same kinds, shapes, alignment with `s.data` and errors; the probabilities are
+    recomputed with it, the forward's bits.  `dbias` (..., nnz) is the derivative with respect to the biased score,
+    `z_i = p_i * (e_i - delta)` (A16), in the order of `s.data` - the caller's order for a column-compressed mask too.  It is
+    always per head, also for a shared bias (whose gradient is its sum over the head axes), so that it is covered by the
+    order contract: written once per element by the row pass, no atomics.  Where the bias is -inf, p = +0.0 and dbias is 0.
 
     A row without stored elements has a `dq` row of +0.0, a column without stored elements `dk` and `dv` rows of +0.0.  A
     row whose forward row is NaN has a NaN `dq` row and hands NaN to the `dk` / `dv` rows of its columns.
@@ -153,6 +216,11 @@ def sparse_attention_grad(s, q, k, v, grad, *, scale=None):
     The order of every operation is fixed (include/sparse_amd.h, A16): the probabilities are recomputed with the forward's
     bits, `dk` and `dv` sum each column's stored elements in stored order - the same bits on every call.  The column grouping
     of the mask is pattern-only state, built once and kept on the array; a second call converts and builds nothing."""
+    return _attention_grad(s, q, k, v, grad, scale, bias, True)
+
+
+def _attention_grad(s, q, k, v, grad, scale, bias, want_dbias):
+    """`sparse_attention_grad`; `want_dbias` False leaves dbias out of the row pass and returns None in its place"""
     from ._softmax import _check_arguments
     from ._utils import check_zero_fill_value
 
@@ -172,41 +240,62 @@ def sparse_attention_grad(s, q, k, v, grad, *, scale=None):
     if tuple(int(n) for n in grad.shape) != lead + (M, Dv):
         raise ValueError(f"shape-mismatch for sparse_attention_grad: `grad` {tuple(grad.shape)} is not the shape of the forward's "
                          f"result {lead + (M, Dv)}")
+    _check_bias(bias, dt, lead, int(s.nnz), "sparse_attention_grad")
     torch_out = any(isinstance(t, torch.Tensor) for t in (q, k, v, grad))
     if s.nnz == 0 or 0 in lead:
         outs = tuple(torch.zeros(lead + shp, dtype=dt, device=s.device) for shp in ((M, D), (N, D), (N, Dv)))
+        if bias is not None:
+            outs += (torch.zeros(lead + (int(s.nnz),), dtype=dt, device=s.device) if want_dbias else None,)
     else:
         data, indices, indptr = _csr_of_mask(s)
         max_row = _longest_row(s, indptr)
         plan = _column_grouping(s, indices, indptr)
         tq, tk, tv, tg = (dev.to_device(t, s.device) for t in (q, k, v, grad))
+        db = None if bias is None else _bias_in_csr_order(s, bias)
         outs = K.attention_grad_rows(indptr, indices, K.convert(data, dt), plan["colptr"], plan["colperm"], plan["colrows"], tq, tk,
-                                     tv, tg, max_row, plan["max_col"], scale=scale)
-    return outs if torch_out else tuple(dev.to_numpy(t) for t in outs)
+                                     tv, tg, max_row, plan["max_col"], scale=scale, bias=db, want_dbias=want_dbias)
+        order = None if bias is None else _bias_order(s)
+        if order is not None and outs[3] is not None:      # back to the caller's order
+            outs = outs[:3] + (K.gather(outs[3].reshape(-1, int(s.nnz)), order["inv"]).reshape(outs[3].shape),)
+    return outs if torch_out else tuple(None if t is None else dev.to_numpy(t) for t in outs)
 
 
 class _SparseAttention(torch.autograd.Function):
     """forward: the fused call of `sparse_attention`; backward: `sparse_attention_grad` (no gradient for the mask or the scale)"""
 
     @staticmethod
-    def forward(ctx, s, scale, q, k, v):
-        ctx.s, ctx.scale = s, scale
-        ctx.save_for_backward(q, k, v)
-        return sparse_attention(s, q.detach(), k.detach(), v.detach(), scale=scale)
+    def forward(ctx, s, scale, q, k, v, bias):
+        ctx.s, ctx.scale, ctx.has_bias = s, scale, bias is not None
+        if bias is None:
+            ctx.save_for_backward(q, k, v)
+            return sparse_attention(s, q.detach(), k.detach(), v.detach(), scale=scale)
+        ctx.save_for_backward(q, k, v, bias)
+        return sparse_attention(s, q.detach(), k.detach(), v.detach(), scale=scale, bias=bias.detach())
 
     @staticmethod
     def backward(ctx, grad):
-        q, k, v = ctx.saved_tensors
-        dq, dk, dv = sparse_attention_grad(ctx.s, q, k, v, grad, scale=ctx.scale)
         need = ctx.needs_input_grad
-        return None, None, dq if need[2] else None, dk if need[3] else None, dv if need[4] else None
+        if not ctx.has_bias:
+            q, k, v = ctx.saved_tensors
+            dq, dk, dv = sparse_attention_grad(ctx.s, q, k, v, grad, scale=ctx.scale)
+            return None, None, dq if need[2] else None, dk if need[3] else None, dv if need[4] else None, None
+        q, k, v, bias = ctx.saved_tensors
+        dq, dk, dv, dbias = _attention_grad(ctx.s, q, k, v, grad, ctx.scale, bias, need[5])
+        if need[5] and dbias.dim() > bias.dim():      # a bias shared by the heads: the one sum outside the written order
+            dbias = torch.sum(dbias, dim=tuple(range(dbias.dim() - 1)))
+        return None, None, dq if need[2] else None, dk if need[3] else None, dv if need[4] else None, dbias if need[5] else None
 
 
-def sparse_attention_autograd(s, q, k, v, *, scale=None):
-    """`sparse_attention(s, q, k, v, scale=scale)` as a differentiable torch function: the forward is that fused call - the
-    same bits -, the backward is `sparse_attention_grad`.  `q`, `k` and `v` are torch tensors; the mask `s` and `scale` get
-    no gradient, and an operand that does not require one gets None."""
-    for name, t in (("q", q), ("k", k), ("v", v)):
+def sparse_attention_autograd(s, q, k, v, *, scale=None, bias=None):
+    """`sparse_attention(s, q, k, v, scale=scale, bias=bias)` as a differentiable torch function: the forward is that fused call
+    - the same bits -, the backward is `sparse_attention_grad`.  `q`, `k` and `v` are torch tensors; the mask `s` and `scale`
+    get no gradient, and an operand that does not require one gets None.
+
+    `bias`: None or a torch tensor as in `sparse_attention` (aligned with `s.data`, added after the scale, -inf masks an
+    element for a head); it is a differentiable input.  Its gradient is `dbias` of `sparse_attention_grad`; for a bias of
+    shape `(nnz,)` shared by several heads it is `torch.sum` of `dbias` over the head axes - this one sum is outside the
+    written order of A16 (torch chooses its order).  `dbias` is not computed when the bias does not require a gradient."""
+    for name, t in (("q", q), ("k", k), ("v", v)) + ((("bias", bias),) if bias is not None else ()):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"sparse_attention_autograd: `{name}` must be a torch tensor, got {type(t).__name__}")
-    return _SparseAttention.apply(s, scale, q, k, v)
+    return _SparseAttention.apply(s, scale, q, k, v, bias)

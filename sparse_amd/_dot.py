@@ -558,7 +558,7 @@ def _tiled_min_rows(row_bytes):
     return 45056 if panels == 1 else max(4096, 40960 // panels)
 
 
-DERIVED_CACHES = ("_mm_plans", "_keys2d", "_tdot_views", "_csr_of_t", "_csr_view", "_csr_twin", "_tiled_layouts", "_spmm_uses", "_nan_memo", "_derived_stamp", "_sddmm_plan", "_mttkrp_plan", "_softmax_plan", "_attention_plan", "_attention_grad_plan", "_t_view", "_coo_view", "_hot_split")
+DERIVED_CACHES = ("_mm_plans", "_keys2d", "_tdot_views", "_csr_of_t", "_csr_view", "_csr_twin", "_tiled_layouts", "_spmm_uses", "_nan_memo", "_derived_stamp", "_sddmm_plan", "_mttkrp_plan", "_softmax_plan", "_attention_plan", "_attention_grad_plan", "_attention_bias_perm", "_t_view", "_coo_view", "_hot_split")
 
 
 def drop_derived(a):

@@ -178,6 +178,11 @@ SIGNATURES = {
     "spamd_attention_ws_bytes": (_i64, [_int, _i64, _i64, _i64, _i64]),
     "spamd_attention": (_int, [_int, _int, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64,
                                _vp, _i64, _i64, _int, _C.c_double, _int, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
+    "spamd_attention_bias": (_int, [_int, _int, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64,
+                                    _vp, _i64, _i64, _int, _C.c_double, _int, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "spamd_attention_grad_bias": (_int, [_int, _int, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                         _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _int, _C.c_double, _int, _int, _i64,
+                                         _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "spamd_attention_grad_ws_bytes": (_i64, [_int, _i64, _i64, _i64, _i64, _i64]),
     "spamd_attention_grad": (_int, [_int, _int, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64,
                                     _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _int, _C.c_double, _int, _int, _i64, _i64,

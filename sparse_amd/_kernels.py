@@ -1749,13 +1749,32 @@ def _rows3(t, dev):
     return t3, pitch, head
 
 
-def attention_rows(indptr, indices, svals, q, k, v, max_len, *, scale=None, group=None, chunk=None, form=None, short_max=None):
+def _bias2(bias, lead, H, nnz, dt, what):
+    """(tensor, head stride in elements) of a bias in CSR order: [nnz] - shared, stride 0 - or lead + [nnz], viewed as (H, nnz)
+    with its own head stride where the strides allow it (a slice of a wider tensor is not copied), else one copy"""
+    if bias.dtype != dt:
+        raise TypeError(f"{what}: the bias must have the type of the operands ({dt}), got {bias.dtype}")
+    shape = tuple(int(n) for n in bias.shape)
+    if shape == (nnz,):
+        return bias.contiguous(), 0
+    if shape != tuple(int(n) for n in lead) + (nnz,):
+        raise ValueError(f"{what}: the bias must have the shape ({nnz},) or {tuple(lead) + (nnz,)}, got {shape}")
+    b2 = bias.reshape(H, nnz)                    # (a view when the leading axes fold into one stride, else the one copy)
+    if nnz > 1 and b2.stride(1) != 1 or H > 1 and b2.stride(0) < nnz:
+        b2 = b2.contiguous()
+    return b2, (int(b2.stride(0)) if H > 1 else 0)
+
+
+def attention_rows(indptr, indices, svals, q, k, v, max_len, *, scale=None, group=None, chunk=None, form=None, short_max=None,
+                   bias=None):
     """out[h] = softmax_over_stored(scale * (s * (q[h] @ k[h].T))) @ v[h] for the CSR mask (`svals`, `indices`, `indptr`: M + 1
     int32 | int64 pointers) (spamd_attention).  `q` [..., M, D], `k` [..., N, D], `v` [..., N, Dv] are device tensors of the
     type of `svals` (float32 or float64) with the same leading axes; `max_len` is the longest row's length.  Returns the
     dense [..., M, Dv] tensor.  `form` forces a kernel form, for tests and sweeps: "short" (sub-groups of `group` lanes; every
     row has at most 64 elements), "wide" (a wave per row; at most `chunk` elements), "long" (a wave per row up to `chunk`,
-    default 64 here, pieces beyond); `short_max` moves the length at which a row goes from a sub-group to a wave (sweeps)."""
+    default 64 here, pieces beyond); `short_max` moves the length at which a row goes from a sub-group to a wave (sweeps).
+    `bias`: None, or a device tensor of that type in the order of `svals`, [nnz] (every head shares it) or [..., nnz], added to
+    the scores after the scale (spamd_attention_bias)."""
     dev = require_hip(indptr, indices, svals, q, k, v)
     dt = svals.dtype
     if dt not in (torch.float32, torch.float64) or any(t.dtype != dt for t in (q, k, v)):
@@ -1787,9 +1806,16 @@ def attention_rows(indptr, indices, svals, q, k, v, max_len, *, scale=None, grou
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
     has_scale = scale is not None
     sc = float(np.asarray(scale).astype(np_dtype(dt))) if has_scale else 0.0
-    _ffi.call("spamd_attention", code_of(dt), code_of(indptr.dtype), M, N, nnz, H, D, Dv, ptr(indptr.contiguous()),
+    if bias is None:
+        _ffi.call("spamd_attention", code_of(dt), code_of(indptr.dtype), M, N, nnz, H, D, Dv, ptr(indptr.contiguous()),
+                  ptr(indices.contiguous()), ptr(svals.contiguous()), ptr(q3), qp, qh, ptr(k3), kp, kh, ptr(v3), vp, vh,
+                  int(has_scale), sc, group, short_max, chunk, max_len, ptr(ws), ws_bytes, ptr(out), stream_ptr(dev))
+        return out
+    require_hip(indptr, bias)
+    b2, bh = _bias2(bias, lead, H, nnz, dt, "attention")      # (nnz == 0: no pointer, which the entry takes for no bias - rightly)
+    _ffi.call("spamd_attention_bias", code_of(dt), code_of(indptr.dtype), M, N, nnz, H, D, Dv, ptr(indptr.contiguous()),
               ptr(indices.contiguous()), ptr(svals.contiguous()), ptr(q3), qp, qh, ptr(k3), kp, kh, ptr(v3), vp, vh,
-              int(has_scale), sc, group, short_max, chunk, max_len, ptr(ws), ws_bytes, ptr(out), stream_ptr(dev))
+              int(has_scale), sc, group, short_max, chunk, max_len, ptr(b2), bh, ptr(ws), ws_bytes, ptr(out), stream_ptr(dev))
     return out
 
 
@@ -1825,8 +1851,10 @@ def attention_grad_chunk():
 
 
 def attention_grad_rows(indptr, indices, svals, colptr, colperm, colrows, q, k, v, g, max_row, max_col, *, scale=None, group=None,
-                        col_group=None, chunk=None, form=None, short_max=None):
-    """(dq, dk, dv) of `attention_rows` for the gradient `g` [..., M, Dv] of its result (spamd_attention_grad).  The mask and
+                        col_group=None, chunk=None, form=None, short_max=None, bias=None, want_dbias=False):
+    """(dq, dk, dv) of `attention_rows` for the gradient `g` [..., M, Dv] of its result (spamd_attention_grad).  With a `bias`
+    (as in `attention_rows`: spamd_attention_grad_bias) the probabilities are the biased forward's and the result is
+    (dq, dk, dv, dbias): dbias [..., nnz] in the order of `svals`, always per head, or None unless `want_dbias`.  The mask and
     q, k, v are as there; `colptr` (N + 1, the type of `indptr`), `colperm` (int64[nnz]) and `colrows` (nnz, the type of
     `indptr`) are the column grouping: the stored positions of every column in stored order and their row ids; `max_row` and
     `max_col` the longest row and column.  `form` forces a kernel form on BOTH passes, for tests and sweeps: "short"
@@ -1870,11 +1898,22 @@ def attention_grad_rows(indptr, indices, svals, colptr, colperm, colrows, q, k, 
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
     has_scale = scale is not None
     sc = float(np.asarray(scale).astype(np_dtype(dt))) if has_scale else 0.0
-    _ffi.call("spamd_attention_grad", code_of(dt), code_of(indptr.dtype), M, N, nnz, H, D, Dv, ptr(indptr.contiguous()),
+    if bias is None:
+        _ffi.call("spamd_attention_grad", code_of(dt), code_of(indptr.dtype), M, N, nnz, H, D, Dv, ptr(indptr.contiguous()),
+                  ptr(indices.contiguous()), ptr(svals.contiguous()), ptr(colptr.contiguous()), ptr(colperm.contiguous()),
+                  ptr(colrows.contiguous()), ptr(q3), qp, qh, ptr(k3), kp, kh, ptr(v3), vp, vh, ptr(g3), gp, gh, int(has_scale), sc,
+                  group, col_group, short_max, chunk, max_row, max_col, ptr(ws), ws_bytes, ptr(dq), ptr(dk), ptr(dv), stream_ptr(dev))
+        return dq, dk, dv
+    require_hip(indptr, bias)
+    b2, bh = _bias2(bias, lead, H, nnz, dt, "attention_grad")
+    # every element is written by the row pass, which the entry skips only when dq, dk and dv are all empty (D = Dv = 0: z = 0)
+    dbias = (torch.zeros if D == 0 and Dv == 0 else torch.empty)(lead + (nnz,), dtype=dt, device=dev) if want_dbias else None
+    _ffi.call("spamd_attention_grad_bias", code_of(dt), code_of(indptr.dtype), M, N, nnz, H, D, Dv, ptr(indptr.contiguous()),
               ptr(indices.contiguous()), ptr(svals.contiguous()), ptr(colptr.contiguous()), ptr(colperm.contiguous()),
               ptr(colrows.contiguous()), ptr(q3), qp, qh, ptr(k3), kp, kh, ptr(v3), vp, vh, ptr(g3), gp, gh, int(has_scale), sc,
-              group, col_group, short_max, chunk, max_row, max_col, ptr(ws), ws_bytes, ptr(dq), ptr(dk), ptr(dv), stream_ptr(dev))
-    return dq, dk, dv
+              group, col_group, short_max, chunk, max_row, max_col, ptr(b2), bh, ptr(dbias), ptr(ws), ws_bytes, ptr(dq), ptr(dk),
+              ptr(dv), stream_ptr(dev))
+    return dq, dk, dv, dbias
 
 
 # ---------------------------------------------------------------------------------------------

@@ -7,7 +7,8 @@
 // stored elements i = 0 .. n-1 in stored order and columns c_i:
 //   w_i  = dot(q[r], k[c_i]) by 64 accumulators: accumulator l starts at +0.0 and takes a_l = fma(q[l + 64 j], k[c_i][l + 64 j],
 //          a_l) for j ascending (an element past D contributes nothing); folded by halving, a[l] = a[l] + a[l + h], h = 32 .. 1
-//   t_i  = s_i * w_i (one multiply);  t_i = scale * t_i (one more) when a scale is given
+//   t_i  = s_i * w_i (one multiply);  t_i = scale * t_i (one more) when a scale is given;  t_i = t_i + b_i (one add, after the
+//          scale) when a bias is given (spamd_attention_bias; B of AtBias<T, B>: the kernels without one compile as before it existed)
 //   p_i  = A14's softmax of t_0 .. t_{n-1} (maximum first, exp_det, 64 accumulators per piece of `chunk`, one division)
 //   out[r, j]: the elements are cut into pieces of `chunk`; a piece starts at +0.0 and takes acc = fma(p_i, v[c_i, j], acc) for
 //          i ascending; the piece sums are added in piece order (the first piece's sum is the start).  An empty row is +0.0.
@@ -50,9 +51,9 @@ struct AtIn {
 };
 
 // ---- short: a sub-group of G lanes per (row, head) ----------------------------------------------------------------------------
-template <typename T, typename I, int G>
+template <typename T, typename I, int G, bool B>
 __global__ void __launch_bounds__(256)
-at_short_kernel(AtIn<T, I> in, int64_t short_max) {
+at_short_kernel(AtIn<T, I> in, int64_t short_max, AtBias<T, B> bz) {
 #pragma clang fp contract(off)
   constexpr int V = 64 / G;
   constexpr int GPB = 256 / G;
@@ -77,6 +78,7 @@ at_short_kernel(AtIn<T, I> in, int64_t short_max) {
         if (i < n) {
           col[r] = (int64_t)in.idx[b + i];
           sv[r] = in.sv[b + i];
+          if constexpr (B) t[r] = bz.b[head * bz.bh + b + i];   // the bias waits where its score will land
         }
       }
       // phase 1: the scores, four elements at a time; r is unrolled so that no register array is indexed
@@ -93,6 +95,7 @@ at_short_kernel(AtIn<T, I> in, int64_t short_max) {
 #pragma unroll
           for (int e = 1; e < 4; ++e) mine = sub == ii + e ? w[e] : mine;
           mine = in.score(sv[r], mine);
+          if constexpr (B) mine = mine + t[r];   // (every live lane passes here once: t[r] is still its bias)
           t[r] = sub >= ii && sub < ii + 4 && sub < cnt ? mine : t[r];   // the lanes that hold these four elements
         }
       }
@@ -148,9 +151,9 @@ at_short_kernel(AtIn<T, I> in, int64_t short_max) {
 }
 
 // ---- wide: a wave (one workgroup) per (row, head), the scores in LDS ------------------------------------------------------------
-template <typename T, typename I>
+template <typename T, typename I, bool B>
 __global__ void __launch_bounds__(64)
-at_wide_kernel(AtIn<T, I> in, int64_t above, int64_t upto) {
+at_wide_kernel(AtIn<T, I> in, int64_t above, int64_t upto, AtBias<T, B> bz) {
 #pragma clang fp contract(off)
   extern __shared__ __attribute__((aligned(16))) unsigned char at_smem[];
   T* __restrict__ lds = reinterpret_cast<T*>(at_smem);   // `upto` values
@@ -183,7 +186,7 @@ at_wide_kernel(AtIn<T, I> in, int64_t above, int64_t upto) {
           if (lane == 0) {
 #pragma unroll
             for (int e = 0; e < 4; ++e)
-              if (i + e < n) lds[i + e] = in.score(in.sv[b + i + e], w[e]);
+              if (i + e < n) lds[i + e] = bz.add(in.score(in.sv[b + i + e], w[e]), head, b + i + e);
           }
         }
         __syncthreads();
@@ -220,8 +223,8 @@ __host__ __device__ __forceinline__ int64_t at_ws_values(int64_t nnz, int64_t nw
   return nnz + 8 * nwin + 2 * nwin * Dv;
 }
 
-template <typename T, typename I, int PHASE>
-__device__ __forceinline__ void at_piece(const AtIn<T, I>& in, int64_t head, int64_t row, int64_t b, int64_t s, int64_t e,
+template <typename T, typename I, int PHASE, bool B>
+__device__ __forceinline__ void at_piece(const AtIn<T, I>& in, const AtBias<T, B>& bz, int64_t head, int64_t row, int64_t b, int64_t s, int64_t e,
                                          int64_t chunk, int64_t nnz, int64_t nwin, int lane, T* __restrict__ ws) {
 #pragma clang fp contract(off)
   T* __restrict__ sc = ws;
@@ -241,7 +244,7 @@ __device__ __forceinline__ void at_piece(const AtIn<T, I>& in, int64_t head, int
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         if (x + u < e) {
-          const T t = in.score(in.sv[x + u], w[u]);
+          const T t = bz.add(in.score(in.sv[x + u], w[u]), head, x + u);
           m = at_nmax(m, t);
           if (lane == 0) sc[x + u] = t;
         }
@@ -287,9 +290,9 @@ __device__ __forceinline__ void at_piece(const AtIn<T, I>& in, int64_t head, int
   }
 }
 
-template <typename T, typename I, int PHASE>
+template <typename T, typename I, int PHASE, bool B>
 __global__ void __launch_bounds__(256)
-at_piece_kernel(AtIn<T, I> in, int64_t nnz, int64_t chunk, int64_t nwin, T* __restrict__ ws_all) {
+at_piece_kernel(AtIn<T, I> in, int64_t nnz, int64_t chunk, int64_t nwin, T* __restrict__ ws_all, AtBias<T, B> bz) {
   const int lane = threadIdx.x & 63;
   const int64_t M = in.M;
   {
@@ -304,13 +307,13 @@ at_piece_kernel(AtIn<T, I> in, int64_t nnz, int64_t chunk, int64_t nwin, T* __re
         if (e0 - b0 > chunk) {
           const int64_t s = b0 + (lo - b0 + chunk - 1) / chunk * chunk;   // the one piece start of this row in [lo, lo + chunk)
           if (s < hi && s < e0)
-            at_piece<T, I, PHASE>(in, head, r0, b0, s, s + chunk < e0 ? s + chunk : e0, chunk, nnz, nwin, lane, ws);
+            at_piece<T, I, PHASE, B>(in, bz, head, r0, b0, s, s + chunk < e0 ? s + chunk : e0, chunk, nnz, nwin, lane, ws);
         }
       }
       const int64_t r1 = at_row_of(in.ptr, M, hi - 1);
       if (r1 > r0) {   // starts inside the window; only the last such row can be longer than the window
         const int64_t b1 = (int64_t)in.ptr[r1], e1 = (int64_t)in.ptr[r1 + 1];
-        if (e1 - b1 > chunk) at_piece<T, I, PHASE>(in, head, r1, b1, b1, b1 + chunk, chunk, nnz, nwin, lane, ws);
+        if (e1 - b1 > chunk) at_piece<T, I, PHASE, B>(in, bz, head, r1, b1, b1, b1 + chunk, chunk, nnz, nwin, lane, ws);
       }
     }
   }
@@ -375,13 +378,13 @@ static unsigned at_grid(int64_t items, int64_t per_block) {
   return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(items, per_block), (int64_t)1 << 20));
 }
 
-template <typename T, typename I>
-static int attention_typed(AtIn<T, I> in, int64_t nnz, int group, int64_t short_max, int64_t chunk, int64_t max_len, void* ws_,
+template <typename T, typename I, bool B>
+static int attention_typed(AtIn<T, I> in, AtBias<T, B> bz, int64_t nnz, int group, int64_t short_max, int64_t chunk, int64_t max_len, void* ws_,
                            hipStream_t st) {
   const unsigned gy = (unsigned)in.H;
   {   // (always: the rows without a stored element are written here)
 #define AT_SHORT(G) \
-  hipLaunchKernelGGL((at_short_kernel<T, I, G>), dim3(at_grid(in.M, 256 / G), gy), dim3(256), 0, st, in, short_max)
+  hipLaunchKernelGGL((at_short_kernel<T, I, G, B>), dim3(at_grid(in.M, 256 / G), gy), dim3(256), 0, st, in, short_max, bz)
     if (group == 8) AT_SHORT(8);
     else if (group == 16) AT_SHORT(16);
     else if (group == 32) AT_SHORT(32);
@@ -390,23 +393,24 @@ static int attention_typed(AtIn<T, I> in, int64_t nnz, int group, int64_t short_
     if (int rc = launch_status()) return rc;
   }
   if (std::min(max_len, chunk) > short_max) {
-    hipLaunchKernelGGL((at_wide_kernel<T, I>), dim3(at_grid(in.M, 64), gy), dim3(64), (size_t)chunk * sizeof(T), st, in, short_max,
-                       chunk);
+    hipLaunchKernelGGL((at_wide_kernel<T, I, B>), dim3(at_grid(in.M, 64), gy), dim3(64), (size_t)chunk * sizeof(T), st, in, short_max,
+                       chunk, bz);
     if (int rc = launch_status()) return rc;
   }
   if (max_len > chunk) {
     T* ws = (T*)ws_;
     const int64_t nwin = ceil_div(nnz, chunk);
     const dim3 pg(at_grid(nwin, 4), gy), jg(at_grid(in.M, 256), gy);
-    hipLaunchKernelGGL((at_piece_kernel<T, I, 0>), pg, dim3(256), 0, st, in, nnz, chunk, nwin, ws);
+    const AtBias<T, false> nob{};   // the biased scores are in the workspace from here on
+    hipLaunchKernelGGL((at_piece_kernel<T, I, 0, B>), pg, dim3(256), 0, st, in, nnz, chunk, nwin, ws, bz);
     if (int rc = launch_status()) return rc;
     hipLaunchKernelGGL((at_join_kernel<T, I, 0>), jg, dim3(256), 0, st, in, nnz, chunk, nwin, ws);
     if (int rc = launch_status()) return rc;
-    hipLaunchKernelGGL((at_piece_kernel<T, I, 1>), pg, dim3(256), 0, st, in, nnz, chunk, nwin, ws);
+    hipLaunchKernelGGL((at_piece_kernel<T, I, 1, false>), pg, dim3(256), 0, st, in, nnz, chunk, nwin, ws, nob);
     if (int rc = launch_status()) return rc;
     hipLaunchKernelGGL((at_join_kernel<T, I, 1>), jg, dim3(256), 0, st, in, nnz, chunk, nwin, ws);
     if (int rc = launch_status()) return rc;
-    hipLaunchKernelGGL((at_piece_kernel<T, I, 2>), pg, dim3(256), 0, st, in, nnz, chunk, nwin, ws);
+    hipLaunchKernelGGL((at_piece_kernel<T, I, 2, false>), pg, dim3(256), 0, st, in, nnz, chunk, nwin, ws, nob);
     if (int rc = launch_status()) return rc;
     hipLaunchKernelGGL((at_join_kernel<T, I, 2>), jg, dim3(256), 0, st, in, nnz, chunk, nwin, ws);
     if (int rc = launch_status()) return rc;
@@ -418,13 +422,18 @@ template <typename T, typename I>
 static int attention_in(int64_t M, int64_t nnz, int64_t H, int64_t D, int64_t Dv, const void* ptr, const void* idx, const void* sv,
                         const void* q, int64_t qp, int64_t qh, const void* k, int64_t kp, int64_t kh, const void* v, int64_t vp,
                         int64_t vh, int has_scale, double scale, int group, int64_t short_max, int64_t chunk, int64_t max_len,
-                        void* ws, void* out, hipStream_t st) {
+                        const void* bias, int64_t bias_head, void* ws, void* out, hipStream_t st) {
   const int64_t ws_head = max_len > chunk ? at_ws_values(nnz, ceil_div(nnz, chunk), Dv) : 0;
   for (int64_t h0 = 0; h0 < H; h0 += 65535) {   // a head per grid.y: at most 65535 of them in one launch
     AtIn<T, I> in{(const I*)ptr, (const I*)idx, (const T*)sv, (const T*)q + h0 * qh, (const T*)k + h0 * kh, (const T*)v + h0 * vh,
                   qp, qh, kp, kh, vp, vh, M, std::min<int64_t>(H - h0, 65535), (int)D, (int)Dv, (T)scale, has_scale != 0,
                   (T*)out + h0 * M * Dv};
-    if (int rc = attention_typed<T, I>(in, nnz, group, short_max, chunk, max_len, ws ? (T*)ws + h0 * ws_head : nullptr, st)) return rc;
+    T* wsh = ws ? (T*)ws + h0 * ws_head : nullptr;
+    int rc;
+    if (bias) rc = attention_typed<T, I, true>(in, AtBias<T, true>{(const T*)bias + h0 * bias_head, bias_head, nullptr}, nnz, group,
+                                               short_max, chunk, max_len, wsh, st);
+    else rc = attention_typed<T, I, false>(in, AtBias<T, false>{}, nnz, group, short_max, chunk, max_len, wsh, st);
+    if (rc) return rc;
   }
   return 0;
 }
@@ -441,16 +450,20 @@ extern "C" int64_t spamd_attention_ws_bytes(int val_dtype, int64_t nnz, int64_t 
   return H * at_ws_values(nnz, ceil_div(nnz, chunk), Dv) * esz;
 }
 
-extern "C" int spamd_attention(int val_dtype, int idx_dtype, int64_t M, int64_t N, int64_t nnz, int64_t H, int64_t D, int64_t Dv,
-                               const void* s_ptr, const void* s_idx, const void* s_val, const void* q, int64_t q_pitch,
-                               int64_t q_head, const void* k, int64_t k_pitch, int64_t k_head, const void* v, int64_t v_pitch,
-                               int64_t v_head, int has_scale, double scale, int group, int64_t short_max, int64_t chunk,
-                               int64_t max_len, void* ws, int64_t ws_bytes, void* out, void* stream) {
+// the entry with an additive bias: b[head * bias_head + pos] (in elements; bias_head = 0: one bias for every head) is added to
+// the score of the stored position pos after the scale.  bias = NULL is spamd_attention
+extern "C" int spamd_attention_bias(int val_dtype, int idx_dtype, int64_t M, int64_t N, int64_t nnz, int64_t H, int64_t D, int64_t Dv,
+                                    const void* s_ptr, const void* s_idx, const void* s_val, const void* q, int64_t q_pitch,
+                                    int64_t q_head, const void* k, int64_t k_pitch, int64_t k_head, const void* v, int64_t v_pitch,
+                                    int64_t v_head, int has_scale, double scale, int group, int64_t short_max, int64_t chunk,
+                                    int64_t max_len, const void* bias, int64_t bias_head, void* ws, int64_t ws_bytes, void* out,
+                                    void* stream) {
   if (val_dtype != SPAMD_F32 && val_dtype != SPAMD_F64) return SPAMD_ETYPE;
   if (idx_dtype != SPAMD_I32 && idx_dtype != SPAMD_I64) return SPAMD_ETYPE;
   if (M < 0 || N < 0 || nnz < 0 || H < 0 || D < 0 || Dv < 0 || max_len < 0 || max_len > nnz) return SPAMD_EINVAL;
   if (D > INT32_MAX - 128 || Dv > INT32_MAX - 128) return SPAMD_EINVAL;   // (row widths are 32-bit in the kernels)
   if (q_pitch < 0 || q_head < 0 || k_pitch < 0 || k_head < 0 || v_pitch < 0 || v_head < 0) return SPAMD_EINVAL;
+  if (bias_head < 0) return SPAMD_EINVAL;
   if (group != 8 && group != 16 && group != 32 && group != 64) return SPAMD_EINVAL;
   if (chunk < 64 || chunk > ATTENTION_MAX_CHUNK || chunk % 64 || short_max < 0 || short_max > 64) return SPAMD_EINVAL;
   if (M == 0 || H == 0 || Dv == 0) return 0;
@@ -461,9 +474,19 @@ extern "C" int spamd_attention(int val_dtype, int idx_dtype, int64_t M, int64_t 
   SPAMD_DISPATCH_IDX(idx_dtype, I, {
     if (val_dtype == SPAMD_F32)
       return attention_in<float, I>(M, nnz, H, D, Dv, s_ptr, s_idx, s_val, q, q_pitch, q_head, k, k_pitch, k_head, v, v_pitch,
-                                    v_head, has_scale, scale, group, short_max, chunk, max_len, ws, out, st);
+                                    v_head, has_scale, scale, group, short_max, chunk, max_len, bias, bias_head, ws, out, st);
     return attention_in<double, I>(M, nnz, H, D, Dv, s_ptr, s_idx, s_val, q, q_pitch, q_head, k, k_pitch, k_head, v, v_pitch,
-                                   v_head, has_scale, scale, group, short_max, chunk, max_len, ws, out, st);
+                                   v_head, has_scale, scale, group, short_max, chunk, max_len, bias, bias_head, ws, out, st);
   })
   return SPAMD_ETYPE;
+}
+
+extern "C" int spamd_attention(int val_dtype, int idx_dtype, int64_t M, int64_t N, int64_t nnz, int64_t H, int64_t D, int64_t Dv,
+                               const void* s_ptr, const void* s_idx, const void* s_val, const void* q, int64_t q_pitch,
+                               int64_t q_head, const void* k, int64_t k_pitch, int64_t k_head, const void* v, int64_t v_pitch,
+                               int64_t v_head, int has_scale, double scale, int group, int64_t short_max, int64_t chunk,
+                               int64_t max_len, void* ws, int64_t ws_bytes, void* out, void* stream) {
+  return spamd_attention_bias(val_dtype, idx_dtype, M, N, nnz, H, D, Dv, s_ptr, s_idx, s_val, q, q_pitch, q_head, k, k_pitch, k_head,
+                              v, v_pitch, v_head, has_scale, scale, group, short_max, chunk, max_len, nullptr, 0, ws, ws_bytes, out,
+                              stream);
 }

@@ -43,6 +43,25 @@ __device__ __forceinline__ T at_neg_inf() {
   return -std::numeric_limits<T>::infinity();
 }
 
+// the additive per-element bias of A15 / A16: b[head * bh + pos] is added to the score of the stored (CSR) position pos, one add
+// after the scale; bh = 0 shares one bias between the heads.  `db` (the backward pass only; may be null) takes z at
+// db[head * nnz + pos].  B = false is an empty argument: the kernels of the entries without a bias compile as before it existed
+template <typename T, bool B>
+struct AtBias {
+  const T* b;
+  int64_t bh;
+  T* db;
+  __device__ __forceinline__ T add(T t, int64_t head, int64_t pos) const {
+#pragma clang fp contract(off)
+    return t + b[head * bh + pos];
+  }
+};
+
+template <typename T>
+struct AtBias<T, false> {
+  __device__ __forceinline__ T add(T t, int64_t, int64_t) const { return t; }
+};
+
 // one block of 64 elements (from e0) of four dot products: a[e][m] = fma(q[l], k_e[l], a[e][m]) at l = e0 + sub + G m.  TAIL: the
 // block may reach past D - such an element is read at D - 1 and not used (no branch around a load)
 template <typename T, int G, bool TAIL>

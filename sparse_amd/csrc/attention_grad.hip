@@ -12,6 +12,7 @@
 //   delta = sum u_i in A14's order: 64 accumulators per piece of `chunk` (accumulator l holds u[l], then adds u[l + 64], ..),
 //          folded by halving, the piece sums added in piece order
 //   z_i  = p_i * (e_i - delta);  y_i = s_i * z_i;  y_i = scale * y_i when a scale is given
+//   dbias[pos_i] = z_i with a bias (spamd_attention_grad_bias): t_i then carries A15's bias step, and the row pass stores z_i once
 //   dq[r, j]: pieces of `chunk`; a piece starts at +0.0 and takes acc = fma(y_i, k[c_i, j], acc), i ascending; piece sums in
 //          piece order
 // Column c of one head, the stored elements of column c in stored order (positions pos_i = cperm[..], rows r_i = crow[..]), cut
@@ -57,10 +58,13 @@ struct AgIn {
     const T t = s * w;
     return has_scale ? scale * t : t;
   }
-  __device__ __forceinline__ T yval(T s, T p, T e, T delta) const {
+  __device__ __forceinline__ T zval(T p, T e, T delta) const {   // the derivative with respect to the score: dbias
 #pragma clang fp contract(off)
     const T d = e - delta;
-    const T z = p * d;
+    return p * d;
+  }
+  __device__ __forceinline__ T yof(T s, T z) const {
+#pragma clang fp contract(off)
     const T y = s * z;
     return has_scale ? scale * y : y;
   }
@@ -99,9 +103,9 @@ __device__ __forceinline__ void ag_gather_acc(const T* __restrict__ vals, const 
 }
 
 // ---- row pass, short: a sub-group of G lanes per (row, head) ---------------------------------------------------------------------
-template <typename T, typename I, int G>
+template <typename T, typename I, int G, bool B>
 __global__ void __launch_bounds__(256)
-ag_short_kernel(AgIn<T, I> in, int64_t short_max) {
+ag_short_kernel(AgIn<T, I> in, int64_t short_max, AtBias<T, B> bz) {
 #pragma clang fp contract(off)
   constexpr int V = 64 / G;
   constexpr int GPB = 256 / G;
@@ -129,6 +133,7 @@ ag_short_kernel(AgIn<T, I> in, int64_t short_max) {
       if (i < n) {
         col[r] = (int64_t)in.idx[b + i];
         sv[r] = in.sv[b + i];
+        if constexpr (B) t[r] = bz.b[head * bz.bh + b + i];   // the bias waits where its score will land
       }
     }
     // phase 1: the scores and e = g[r] . v[c], four elements at a time; r is unrolled so that no register array is indexed
@@ -154,6 +159,7 @@ ag_short_kernel(AgIn<T, I> in, int64_t short_max) {
           minx = sub == ii + e ? x[e] : minx;
         }
         mine = in.score(sv[r], mine);
+        if constexpr (B) mine = mine + t[r];   // (every live lane passes here once: t[r] is still its bias)
         const bool here = sub >= ii && sub < ii + 4 && sub < cnt;   // the lanes that hold these four elements
         t[r] = here ? mine : t[r];
         ev[r] = here ? minx : ev[r];
@@ -189,10 +195,13 @@ ag_short_kernel(AgIn<T, I> in, int64_t short_max) {
 #pragma unroll
     for (int r = 0; r < V; ++r) {
       const int i = sub + r * G;
-      ev[r] = in.yval(sv[r], t[r], ev[r], delta);   // ev holds y from here on
+      const T z = in.zval(t[r], ev[r], delta);
+      ev[r] = in.yof(sv[r], z);   // ev holds y from here on
       if (i < n) {
         wp[b + i] = t[r];
         wy[b + i] = ev[r];
+        if constexpr (B)
+          if (bz.db) bz.db[head * in.nnz + b + i] = z;
       }
     }
     // phase 4: the dq row, 64 columns at a time (lane u: the columns u, u + G, ..), four k rows in flight
@@ -227,9 +236,9 @@ ag_short_kernel(AgIn<T, I> in, int64_t short_max) {
 }
 
 // ---- row pass, wide: a wave (one workgroup) per (row, head), t / p and e / y in LDS -------------------------------------------------
-template <typename T, typename I>
+template <typename T, typename I, bool B>
 __global__ void __launch_bounds__(64)
-ag_wide_kernel(AgIn<T, I> in, int64_t above, int64_t upto) {
+ag_wide_kernel(AgIn<T, I> in, int64_t above, int64_t upto, AtBias<T, B> bz) {
 #pragma clang fp contract(off)
   extern __shared__ __attribute__((aligned(16))) unsigned char ag_smem[];
   T* __restrict__ lt = reinterpret_cast<T*>(ag_smem);   // `upto` values: t, then p
@@ -267,7 +276,7 @@ ag_wide_kernel(AgIn<T, I> in, int64_t above, int64_t upto) {
         if (lane == 0) {
 #pragma unroll
           for (int e = 0; e < 4; ++e)
-            if (i + e < n) lt[i + e] = in.score(in.sv[b + i + e], w[e]);
+            if (i + e < n) lt[i + e] = bz.add(in.score(in.sv[b + i + e], w[e]), head, b + i + e);
         }
       }
       for (int i = 0; i < n; i += 4) {   // e = g[r] . v[c] (a loop of its own: half as many wave-uniform pointers live)
@@ -303,10 +312,13 @@ ag_wide_kernel(AgIn<T, I> in, int64_t above, int64_t upto) {
       }
       const T delta = at_xsum<T, 64>(acc);
       for (int x = lane; x < n; x += 64) {
-        const T y = in.yval(in.sv[b + x], lt[x], le[x], delta);
+        const T z = in.zval(lt[x], le[x], delta);
+        const T y = in.yof(in.sv[b + x], z);
         le[x] = y;
         wp[b + x] = lt[x];
         wy[b + x] = y;
+        if constexpr (B)
+          if (bz.db) bz.db[head * in.nnz + b + x] = z;
       }
       __syncthreads();
       T* __restrict__ orow = in.dq + (head * in.M + row) * in.D;
@@ -330,8 +342,8 @@ __host__ __device__ __forceinline__ int64_t ag_ws_values(int64_t nnz, int64_t nw
 }
 
 // row phases: 0 t, e and piece maxima; 1 piece sums of exp; 2 p and piece deltas; 3 y; 4 dq pieces.  Column phase: 5 dv | dk pieces
-template <typename T, typename I, int PHASE>
-__device__ __forceinline__ void ag_piece(const AgIn<T, I>& in, int64_t head, int64_t row, int64_t b, int64_t s, int64_t e,
+template <typename T, typename I, int PHASE, bool B>
+__device__ __forceinline__ void ag_piece(const AgIn<T, I>& in, const AtBias<T, B>& bz, int64_t head, int64_t row, int64_t b, int64_t s, int64_t e,
                                          int64_t chunk, int64_t nwin, int lane, T* __restrict__ ws) {
 #pragma clang fp contract(off)
   T* __restrict__ wp = ws;
@@ -361,7 +373,7 @@ __device__ __forceinline__ void ag_piece(const AgIn<T, I>& in, int64_t head, int
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         if (x + u < e) {
-          const T t = in.score(in.sv[x + u], w[u]);
+          const T t = bz.add(in.score(in.sv[x + u], w[u]), head, x + u);
           m = at_nmax(m, t);
           if (lane == 0) {
             wp[x + u] = t;
@@ -390,7 +402,13 @@ __device__ __forceinline__ void ag_piece(const AgIn<T, I>& in, int64_t head, int
     if (lane == 0) st[8 * nwin + slot] = acc;
   } else if (PHASE == 3) {
     const T delta = st[10 * nwin + slot0];
-    for (int64_t x = s + lane; x < e; x += 64) wy[x] = in.yval(in.sv[x], wp[x], wy[x], delta);
+    for (int64_t x = s + lane; x < e; x += 64) {
+      const T s_x = in.sv[x];
+      const T z = in.zval(wp[x], wy[x], delta);
+      wy[x] = in.yof(s_x, z);
+      if constexpr (B)
+        if (bz.db) bz.db[head * in.nnz + x] = z;
+    }
   } else if (PHASE == 4) {
     const T* __restrict__ kh = in.k + head * in.kh;
     for (int jb = 0; jb < in.D; jb += 64) {
@@ -415,9 +433,9 @@ __device__ __forceinline__ void ag_piece(const AgIn<T, I>& in, int64_t head, int
 }
 
 // a wave per window of `chunk` positions: the window holds at most two piece starts of long rows (csrc/attention.hip)
-template <typename T, typename I, int PHASE>
+template <typename T, typename I, int PHASE, bool B>
 __global__ void __launch_bounds__(256)
-ag_piece_kernel(AgIn<T, I> in, int64_t chunk, int64_t nwin) {
+ag_piece_kernel(AgIn<T, I> in, int64_t chunk, int64_t nwin, AtBias<T, B> bz) {
   const int lane = threadIdx.x & 63;
   const I* __restrict__ ptr = PHASE == 5 ? in.cptr : in.ptr;
   const int64_t R = PHASE == 5 ? in.N : in.M, nnz = in.nnz;
@@ -431,13 +449,13 @@ ag_piece_kernel(AgIn<T, I> in, int64_t chunk, int64_t nwin) {
       const int64_t b0 = (int64_t)ptr[r0], e0 = (int64_t)ptr[r0 + 1];
       if (e0 - b0 > chunk) {
         const int64_t s = b0 + (lo - b0 + chunk - 1) / chunk * chunk;   // the one piece start of this row in [lo, lo + chunk)
-        if (s < hi && s < e0) ag_piece<T, I, PHASE>(in, head, r0, b0, s, s + chunk < e0 ? s + chunk : e0, chunk, nwin, lane, ws);
+        if (s < hi && s < e0) ag_piece<T, I, PHASE, B>(in, bz, head, r0, b0, s, s + chunk < e0 ? s + chunk : e0, chunk, nwin, lane, ws);
       }
     }
     const int64_t r1 = at_row_of(ptr, R, hi - 1);
     if (r1 > r0) {   // starts inside the window; only the last such row can be longer than the window
       const int64_t b1 = (int64_t)ptr[r1], e1 = (int64_t)ptr[r1 + 1];
-      if (e1 - b1 > chunk) ag_piece<T, I, PHASE>(in, head, r1, b1, b1, b1 + chunk, chunk, nwin, lane, ws);
+      if (e1 - b1 > chunk) ag_piece<T, I, PHASE, B>(in, bz, head, r1, b1, b1, b1 + chunk, chunk, nwin, lane, ws);
     }
   }
 }
@@ -563,30 +581,32 @@ static unsigned ag_grid(int64_t items, int64_t per_block) {
     if (int rc = launch_status()) return rc;                              \
   } while (0)
 
-template <typename T, typename I>
-static int attention_grad_typed(AgIn<T, I> in, int group, int col_group, int64_t short_max, int64_t chunk, int64_t max_row,
+template <typename T, typename I, bool B>
+static int attention_grad_typed(AgIn<T, I> in, AtBias<T, B> bz, int group, int col_group, int64_t short_max, int64_t chunk, int64_t max_row,
                                 int64_t max_col, hipStream_t st) {
   const unsigned gy = (unsigned)in.H;
   const int64_t nwin = ceil_div(in.nnz, chunk);
   const dim3 pg(ag_grid(nwin, 4), gy);
+  const AtBias<T, false> nob{};   // the launches that neither form a score nor hold z
   if (in.M > 0) {   // the row pass; the short form always runs: it writes the dq rows of the rows without a stored element
     const dim3 sg(ag_grid(in.M, 256 / group), gy);
-    if (group == 8) AG_LAUNCH((ag_short_kernel<T, I, 8>), sg, dim3(256), 0, in, short_max);
-    else if (group == 16) AG_LAUNCH((ag_short_kernel<T, I, 16>), sg, dim3(256), 0, in, short_max);
-    else if (group == 32) AG_LAUNCH((ag_short_kernel<T, I, 32>), sg, dim3(256), 0, in, short_max);
-    else AG_LAUNCH((ag_short_kernel<T, I, 64>), sg, dim3(256), 0, in, short_max);
+    if (group == 8) AG_LAUNCH((ag_short_kernel<T, I, 8, B>), sg, dim3(256), 0, in, short_max, bz);
+    else if (group == 16) AG_LAUNCH((ag_short_kernel<T, I, 16, B>), sg, dim3(256), 0, in, short_max, bz);
+    else if (group == 32) AG_LAUNCH((ag_short_kernel<T, I, 32, B>), sg, dim3(256), 0, in, short_max, bz);
+    else AG_LAUNCH((ag_short_kernel<T, I, 64, B>), sg, dim3(256), 0, in, short_max, bz);
     if (std::min(max_row, chunk) > short_max)
-      AG_LAUNCH((ag_wide_kernel<T, I>), dim3(ag_grid(in.M, 64), gy), dim3(64), (size_t)(2 * chunk) * sizeof(T), in, short_max, chunk);
+      AG_LAUNCH((ag_wide_kernel<T, I, B>), dim3(ag_grid(in.M, 64), gy), dim3(64), (size_t)(2 * chunk) * sizeof(T), in, short_max, chunk,
+                bz);
     if (max_row > chunk) {
       const dim3 jg(ag_grid(in.M, 256), gy);
-      AG_LAUNCH((ag_piece_kernel<T, I, 0>), pg, dim3(256), 0, in, chunk, nwin);
+      AG_LAUNCH((ag_piece_kernel<T, I, 0, B>), pg, dim3(256), 0, in, chunk, nwin, bz);
       AG_LAUNCH((ag_join_kernel<T, I, 0>), jg, dim3(256), 0, in, chunk, nwin);
-      AG_LAUNCH((ag_piece_kernel<T, I, 1>), pg, dim3(256), 0, in, chunk, nwin);
+      AG_LAUNCH((ag_piece_kernel<T, I, 1, false>), pg, dim3(256), 0, in, chunk, nwin, nob);
       AG_LAUNCH((ag_join_kernel<T, I, 1>), jg, dim3(256), 0, in, chunk, nwin);
-      AG_LAUNCH((ag_piece_kernel<T, I, 2>), pg, dim3(256), 0, in, chunk, nwin);
+      AG_LAUNCH((ag_piece_kernel<T, I, 2, false>), pg, dim3(256), 0, in, chunk, nwin, nob);
       AG_LAUNCH((ag_join_kernel<T, I, 2>), jg, dim3(256), 0, in, chunk, nwin);
-      AG_LAUNCH((ag_piece_kernel<T, I, 3>), pg, dim3(256), 0, in, chunk, nwin);
-      AG_LAUNCH((ag_piece_kernel<T, I, 4>), pg, dim3(256), 0, in, chunk, nwin);
+      AG_LAUNCH((ag_piece_kernel<T, I, 3, B>), pg, dim3(256), 0, in, chunk, nwin, bz);
+      AG_LAUNCH((ag_piece_kernel<T, I, 4, false>), pg, dim3(256), 0, in, chunk, nwin, nob);
       AG_LAUNCH((ag_join_kernel<T, I, 3>), jg, dim3(256), 0, in, chunk, nwin);
     }
   }
@@ -599,7 +619,7 @@ static int attention_grad_typed(AgIn<T, I> in, int group, int col_group, int64_t
     if (std::min(max_col, chunk) > short_max)
       AG_LAUNCH((ag_col_kernel<T, I, 64>), dim3(ag_grid(in.N, 4), gy), dim3(256), 0, in, short_max, chunk);
     if (max_col > chunk) {
-      AG_LAUNCH((ag_piece_kernel<T, I, 5>), pg, dim3(256), 0, in, chunk, nwin);
+      AG_LAUNCH((ag_piece_kernel<T, I, 5, false>), pg, dim3(256), 0, in, chunk, nwin, nob);
       AG_LAUNCH((ag_join_kernel<T, I, 4>), dim3(ag_grid(in.N, 256), gy), dim3(256), 0, in, chunk, nwin);
     }
   }
@@ -616,6 +636,9 @@ struct AgArgs {
   int group, col_group;
   int64_t short_max, chunk, max_row, max_col;
   void *ws, *dq, *dk, *dv;
+  const void* bias;
+  int64_t bias_head;
+  void* dbias;
 };
 
 template <typename T, typename I>
@@ -628,7 +651,15 @@ static int attention_grad_in(const AgArgs& a, hipStream_t st) {
                   std::min<int64_t>(a.H - h0, 65535), a.nnz, (int)a.D, (int)a.Dv, (T)a.scale, a.has_scale != 0,
                   a.ws ? (T*)a.ws + h0 * ws_head : nullptr, ws_head, (T*)a.dq + h0 * a.M * a.D, (T*)a.dk + h0 * a.N * a.D,
                   (T*)a.dv + h0 * a.N * a.Dv};
-    if (int rc = attention_grad_typed<T, I>(in, a.group, a.col_group, a.short_max, a.chunk, a.max_row, a.max_col, st)) return rc;
+    int rc;
+    if (a.bias)
+      rc = attention_grad_typed<T, I, true>(in, AtBias<T, true>{(const T*)a.bias + h0 * a.bias_head, a.bias_head,
+                                                                 a.dbias ? (T*)a.dbias + h0 * a.nnz : nullptr},
+                                            a.group, a.col_group, a.short_max, a.chunk, a.max_row, a.max_col, st);
+    else
+      rc = attention_grad_typed<T, I, false>(in, AtBias<T, false>{}, a.group, a.col_group, a.short_max, a.chunk, a.max_row, a.max_col,
+                                             st);
+    if (rc) return rc;
   }
   return 0;
 }
@@ -644,13 +675,16 @@ extern "C" int64_t spamd_attention_grad_ws_bytes(int val_dtype, int64_t nnz, int
   return H * ag_ws_values(nnz, nnz > chunk ? ceil_div(nnz, chunk) : 0, D, Dv) * esz;
 }
 
-extern "C" int spamd_attention_grad(int val_dtype, int idx_dtype, int64_t M, int64_t N, int64_t nnz, int64_t H, int64_t D,
+// the entry with an additive bias (spamd_attention_bias): t_i and p_i are recomputed with it, and dbias (H, nnz) contiguous, when
+// not NULL, takes z_i at [head][stored position].  bias = NULL is spamd_attention_grad (dbias is not written)
+extern "C" int spamd_attention_grad_bias(int val_dtype, int idx_dtype, int64_t M, int64_t N, int64_t nnz, int64_t H, int64_t D,
                                     int64_t Dv, const void* s_ptr, const void* s_idx, const void* s_val, const void* c_ptr,
                                     const int64_t* c_perm, const void* c_row, const void* q, int64_t q_pitch, int64_t q_head,
                                     const void* k, int64_t k_pitch, int64_t k_head, const void* v, int64_t v_pitch,
                                     int64_t v_head, const void* g, int64_t g_pitch, int64_t g_head, int has_scale, double scale,
                                     int group, int col_group, int64_t short_max, int64_t chunk, int64_t max_row, int64_t max_col,
-                                    void* ws, int64_t ws_bytes, void* dq, void* dk, void* dv, void* stream) {
+                                    const void* bias, int64_t bias_head, void* dbias, void* ws, int64_t ws_bytes, void* dq, void* dk,
+                                    void* dv, void* stream) {
   if (val_dtype != SPAMD_F32 && val_dtype != SPAMD_F64) return SPAMD_ETYPE;
   if (idx_dtype != SPAMD_I32 && idx_dtype != SPAMD_I64) return SPAMD_ETYPE;
   if (M < 0 || N < 0 || nnz < 0 || H < 0 || D < 0 || Dv < 0) return SPAMD_EINVAL;
@@ -658,6 +692,7 @@ extern "C" int spamd_attention_grad(int val_dtype, int idx_dtype, int64_t M, int
   if (D > INT32_MAX - 128 || Dv > INT32_MAX - 128 - D) return SPAMD_EINVAL;   // (row widths, and D + Dv, are 32-bit in the kernels)
   if (q_pitch < 0 || q_head < 0 || k_pitch < 0 || k_head < 0 || v_pitch < 0 || v_head < 0 || g_pitch < 0 || g_head < 0)
     return SPAMD_EINVAL;
+  if (bias_head < 0) return SPAMD_EINVAL;
   if (group != 8 && group != 16 && group != 32 && group != 64) return SPAMD_EINVAL;
   if (col_group != 8 && col_group != 16 && col_group != 32 && col_group != 64) return SPAMD_EINVAL;
   if (chunk < 64 || chunk > ATTENTION_MAX_CHUNK || chunk % 64 || short_max < 0 || short_max > 64) return SPAMD_EINVAL;
@@ -672,11 +707,23 @@ extern "C" int spamd_attention_grad(int val_dtype, int idx_dtype, int64_t M, int
   }
   const AgArgs a{M, N, nnz, H, D, Dv, s_ptr, s_idx, s_val, c_ptr, c_perm, c_row, q, k, v, g, q_pitch, q_head, k_pitch, k_head,
                  v_pitch, v_head, g_pitch, g_head, has_scale, scale, group, col_group, short_max, chunk, max_row, max_col, ws, dq,
-                 dk, dv};
+                 dk, dv, bias, bias_head, dbias};
   hipStream_t st = (hipStream_t)stream;
   SPAMD_DISPATCH_IDX(idx_dtype, I, {
     if (val_dtype == SPAMD_F32) return attention_grad_in<float, I>(a, st);
     return attention_grad_in<double, I>(a, st);
   })
   return SPAMD_ETYPE;
+}
+
+extern "C" int spamd_attention_grad(int val_dtype, int idx_dtype, int64_t M, int64_t N, int64_t nnz, int64_t H, int64_t D,
+                                    int64_t Dv, const void* s_ptr, const void* s_idx, const void* s_val, const void* c_ptr,
+                                    const int64_t* c_perm, const void* c_row, const void* q, int64_t q_pitch, int64_t q_head,
+                                    const void* k, int64_t k_pitch, int64_t k_head, const void* v, int64_t v_pitch,
+                                    int64_t v_head, const void* g, int64_t g_pitch, int64_t g_head, int has_scale, double scale,
+                                    int group, int col_group, int64_t short_max, int64_t chunk, int64_t max_row, int64_t max_col,
+                                    void* ws, int64_t ws_bytes, void* dq, void* dk, void* dv, void* stream) {
+  return spamd_attention_grad_bias(val_dtype, idx_dtype, M, N, nnz, H, D, Dv, s_ptr, s_idx, s_val, c_ptr, c_perm, c_row, q, q_pitch,
+                                   q_head, k, k_pitch, k_head, v, v_pitch, v_head, g, g_pitch, g_head, has_scale, scale, group,
+                                   col_group, short_max, chunk, max_row, max_col, nullptr, 0, nullptr, ws, ws_bytes, dq, dk, dv, stream);
 }

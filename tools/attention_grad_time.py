@@ -6,6 +6,10 @@ a user had to write before - in the same process, on the same inputs, a Python l
     dq = Y @ k;  dk = Y.T @ q;  dv = P.T @ g
 
     python tools/attention_grad_time.py [--reps 20] [--rounds 5] [--sweep] [--sizes graph heads hub hubcol small]
+                                        [--bias none|shared|head]
+
+  --bias shared | head: with an additive bias b (a sparse array of the mask's pattern in the composed expression, where
+  P = softmax(sddmm(s, q, bt=k) * c + b) and dbias = Z is one more result), beside the fused call without a bias.
 
   sizes (a) graph, (b) heads, (c) hub and (d) small are those of tools/attention_time.py; hubcol is the transpose of (c): ONE hub
   COLUMN of 10^6 stored elements among 2^16 columns of 8.  The hub cases are reported only.
@@ -28,7 +32,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import sparse_amd  # noqa: E402
-from attention_time import build as build_forward, rounds_of, wall_ms  # noqa: E402
+from attention_time import build as build_forward, make_bias, rounds_of, wall_ms  # noqa: E402
 from sparse_amd import _attention, _kernels as K  # noqa: E402
 
 
@@ -43,22 +47,26 @@ def build(tag, d):
     return s, pattern, q, k, v, g, scale
 
 
-def composed_head(s, pattern, q, k, v, g, scale):
-    P = sparse_amd.softmax(sparse_amd.sddmm(s, q, bt=k), -1, scale=scale)
+def composed_head(s, pattern, q, k, v, g, scale, b=None):
+    if b is None:
+        P = sparse_amd.softmax(sparse_amd.sddmm(s, q, bt=k), -1, scale=scale)
+    else:
+        P = sparse_amd.softmax(sparse_amd.sddmm(s, q, bt=k) * scale + b, -1)
     E = sparse_amd.sddmm(pattern, g, bt=v)
     U = P * E
     delta = U.sum(axis=1)
     delta = delta.todense() if hasattr(delta, "todense") else delta
     Z = U - P * delta[:, None]
     Y = (s * Z) * scale
-    return sparse_amd.matmul(Y, k), sparse_amd.matmul(Y.T, q), sparse_amd.matmul(P.T, g)
+    return (sparse_amd.matmul(Y, k), sparse_amd.matmul(Y.T, q), sparse_amd.matmul(P.T, g)) + (() if b is None else (Z,))
 
 
-def composed(s, pattern, q, k, v, g, scale):
+def composed(s, pattern, q, k, v, g, scale, sp=None):
+    """(dq, dk, dv), and with a bias the elementwise dbias (a sparse array per head) as a fourth result"""
     if q.ndim == 2:
-        return composed_head(s, pattern, q, k, v, g, scale)
-    outs = [composed_head(s, pattern, q[h], k[h], v[h], g[h], scale) for h in range(q.shape[0])]
-    return tuple(torch.stack([torch.as_tensor(o[i]) for o in outs]) for i in range(3))
+        return composed_head(s, pattern, q, k, v, g, scale, None if sp is None else sp[0])
+    outs = [composed_head(s, pattern, q[h], k[h], v[h], g[h], scale, None if sp is None else sp[h]) for h in range(q.shape[0])]
+    return tuple(torch.stack([torch.as_tensor(o[i]) for o in outs]) for i in range(3)) + (() if sp is None else ([o[3] for o in outs],))
 
 
 def traffic(s, H, D, Dv, esz, isz):
@@ -70,12 +78,38 @@ def traffic(s, H, D, Dv, esz, isz):
     return {"row_pass_bytes_per_element_head": round(row, 1), "column_pass_bytes_per_element_head": round(col, 1)}
 
 
+def bias_case(args, base, s, pattern, q, k, v, g, scale):
+    b, sp = make_bias(args.bias, s, q)
+    fused_call = lambda: sparse_amd.sparse_attention_grad(s, q, k, v, g, scale=scale, bias=b)                 # noqa: E731
+    first = wall_ms(fused_call)
+    plan, max_row = s._attention_grad_plan, s._attention_plan["max_len"]
+    reps = max(args.reps // 4, 2) if base["size"] in ("hub", "hubcol") else args.reps
+    fused = rounds_of(fused_call, reps, args.rounds)
+    plain = rounds_of(lambda: sparse_amd.sparse_attention_grad(s, q, k, v, g, scale=scale), reps, args.rounds)
+    data, indices, indptr = _attention._csr_of_mask(s)
+    kernel = rounds_of(lambda: K.attention_grad_rows(indptr, indices, data, plan["colptr"], plan["colperm"], plan["colrows"], q, k, v,
+                                                     g, max_row, plan["max_col"], scale=scale, bias=b, want_dbias=True),
+                       reps, args.rounds)
+    first_c = wall_ms(lambda: composed(s, pattern, q, k, v, g, scale, sp))
+    comp = rounds_of(lambda: composed(s, pattern, q, k, v, g, scale, sp), reps, args.rounds)
+    got, ref = fused_call(), composed(s, pattern, q, k, v, g, scale, sp)
+    dev = q.device
+    diff = [float((a.double() - torch.as_tensor(np.asarray(r) if not isinstance(r, torch.Tensor) else r).to(dev).double()).abs().max())
+            for a, r in zip(got[:3], ref[:3])]
+    print(json.dumps({**base, "what": "attention_grad_bias", "bias": args.bias, "max_row": max_row, "max_col": plan["max_col"],
+                      "first_call_wall_ms": first, "fused": fused, "kernels_alone": kernel, "fused_without_bias": plain,
+                      "bias_over_none": round(fused["ms"] / plain["ms"], 3), "composed_first_wall_ms": first_c, "composed": comp,
+                      "composed_over_fused": round(comp["ms"] / fused["ms"], 2), "fused_not_slower": fused["ms"] <= comp["ms"],
+                      "max_abs_diff_dq_dk_dv": diff}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--sizes", nargs="*", default=["graph", "heads", "hub", "hubcol", "small"])
     ap.add_argument("--sweep", action="store_true")
+    ap.add_argument("--bias", choices=["none", "shared", "head"], default="none")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("attention_grad_time.py measures on the GPU: no HIP device visible")
@@ -87,6 +121,9 @@ def main():
         s, pattern, q, k, v, g, scale = build(tag, d)
         H = 1 if q.ndim == 2 else int(q.shape[0])
         base = {"size": tag, "shape": s.shape, "nnz": s.nnz, "heads": H, "D": int(q.shape[-1]), "Dv": int(v.shape[-1])}
+        if args.bias != "none":
+            bias_case(args, base, s, pattern, q, k, v, g, scale)
+            continue
         fused_call = lambda: sparse_amd.sparse_attention_grad(s, q, k, v, g, scale=scale)                 # noqa: E731
         first = wall_ms(fused_call)
         plan, max_row = s._attention_grad_plan, s._attention_plan["max_len"]

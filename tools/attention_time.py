@@ -4,7 +4,13 @@
 
 through this library, in the same process, on the same inputs (the yardstick: it is what a user wrote before):
 
-    python tools/attention_time.py [--reps 20] [--rounds 5] [--sweep] [--sizes graph heads hub small]
+    python tools/attention_time.py [--reps 20] [--rounds 5] [--sweep] [--sizes graph heads hub small] [--bias none|shared|head]
+
+  --bias shared | head: the calls with an additive bias per stored element (one for all heads, or one per head), beside
+
+    matmul(softmax(sddmm(s, q, bt=k) * c + b), v)         with b a sparse array of the mask's pattern
+
+  and beside the fused call without a bias (`bias_over_none`, reported only).
 
   size (a) graph  a CSR graph of 2^17 nodes, mean degree 32 (row lengths Poisson), D = Dv = 64, float32
   size (b) heads  the same graph, H = 8 heads of D = Dv = 16, against a Python loop of the expression over the heads
@@ -87,11 +93,47 @@ def build(tag, d):
     return s, q, k, v, D ** -0.5
 
 
-def three_calls(s, q, k, v, scale):
+def make_bias(mode, s, q):
+    """(the bias tensor for the fused call, its sparse arrays of the mask's pattern for the composed expression: one per head)"""
+    if mode == "none":
+        return None, None
+    H = 1 if q.ndim == 2 else int(q.shape[0])
+    lead = tuple(q.shape[:-2]) if mode == "head" else ()
+    b = torch.randn(lead + (s.nnz,), device=q.device, generator=torch.Generator(q.device).manual_seed(11))
+    rows = b.reshape(-1, s.nnz)
+    sp = [sparse_amd.GCXS((rows[h % rows.shape[0]].contiguous(), s.indices, s.indptr), shape=s.shape, compressed_axes=(0,))
+          for h in range(H)]
+    return b, sp
+
+
+def three_calls(s, q, k, v, scale, sp=None):
+    if sp is not None:
+        one = lambda q, k, v, b: sparse_amd.matmul(sparse_amd.softmax(sparse_amd.sddmm(s, q, bt=k) * scale + b, -1), v)   # noqa: E731
+        return one(q, k, v, sp[0]) if q.ndim == 2 else torch.stack([one(q[h], k[h], v[h], sp[h]) for h in range(q.shape[0])])
     if q.ndim == 2:
         return sparse_amd.matmul(sparse_amd.softmax(sparse_amd.sddmm(s, q, bt=k), -1, scale=scale), v)
     return torch.stack([sparse_amd.matmul(sparse_amd.softmax(sparse_amd.sddmm(s, q[h], bt=k[h]), -1, scale=scale), v[h])
                         for h in range(q.shape[0])])
+
+
+def bias_case(args, base, s, q, k, v, scale):
+    b, sp = make_bias(args.bias, s, q)
+    first = wall_ms(lambda: sparse_amd.sparse_attention(s, q, k, v, scale=scale, bias=b))
+    max_len = s._attention_plan["max_len"]
+    reps = max(args.reps // 4, 2) if base["size"] == "hub" else args.reps
+    fused = rounds_of(lambda: sparse_amd.sparse_attention(s, q, k, v, scale=scale, bias=b), reps, args.rounds)
+    plain = rounds_of(lambda: sparse_amd.sparse_attention(s, q, k, v, scale=scale), reps, args.rounds)
+    data, indices, indptr = _attention._csr_of_mask(s)
+    kernel = rounds_of(lambda: K.attention_rows(indptr, indices, data, q, k, v, max_len, scale=scale, bias=b), reps, args.rounds)
+    first3 = wall_ms(lambda: three_calls(s, q, k, v, scale, sp))
+    three = rounds_of(lambda: three_calls(s, q, k, v, scale, sp), reps, args.rounds)
+    got, ref = sparse_amd.sparse_attention(s, q, k, v, scale=scale, bias=b), three_calls(s, q, k, v, scale, sp)
+    ref = ref if isinstance(ref, torch.Tensor) else torch.from_numpy(np.asarray(ref)).to(q.device)
+    print(json.dumps({**base, "what": "attention_bias", "bias": args.bias, "max_len": max_len, "first_call_wall_ms": first,
+                      "fused": fused, "kernel_alone": kernel, "fused_without_bias": plain,
+                      "bias_over_none": round(fused["ms"] / plain["ms"], 3), "composed_first_wall_ms": first3, "composed": three,
+                      "composed_over_fused": round(three["ms"] / fused["ms"], 2), "fused_not_slower": fused["ms"] <= three["ms"],
+                      "max_abs_diff": float((got.double() - ref.double()).abs().max())}), flush=True)
 
 
 def main():
@@ -100,6 +142,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--sizes", nargs="*", default=["graph", "heads", "hub", "small"])
     ap.add_argument("--sweep", action="store_true")
+    ap.add_argument("--bias", choices=["none", "shared", "head"], default="none")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("attention_time.py measures on the GPU: no HIP device visible")
@@ -111,6 +154,9 @@ def main():
         s, q, k, v, scale = build(tag, d)
         base = {"size": tag, "shape": s.shape, "nnz": s.nnz, "heads": 1 if q.ndim == 2 else int(q.shape[0]), "D": int(q.shape[-1]),
                 "Dv": int(v.shape[-1])}
+        if args.bias != "none":
+            bias_case(args, base, s, q, k, v, scale)
+            continue
         first = wall_ms(lambda: sparse_amd.sparse_attention(s, q, k, v, scale=scale))
         max_len = s._attention_plan["max_len"]
         reps = max(args.reps // 4, 2) if tag == "hub" else args.reps

@@ -6,7 +6,8 @@ A case draws: float32 | float64 operands, 32- | 64-bit indices, a chunk of 64 ..
 lengths (hubs beyond the chunk among many short rows), a share of empty rows, D and Dv of 1 .. 140, no head axis or one or two,
 float, integer or boolean mask values, a query spread of 1 or 8, now and then a scale, a stored zero, an infinity or a NaN among
 the mask values - and the mask as a COO, a COO built unsorted, a CSR or a CSC; the operands as NumPy arrays, device tensors or
-row-strided device views.  Prints one line per case; exits 1 at the first difference."""
+row-strided device views; in half of the cases an additive bias, shared or per head, in the order of the array the caller holds,
+with -inf entries in some.  Prints one line per case; exits 1 at the first difference."""
 import argparse
 import os
 import sys
@@ -17,7 +18,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import attention_bias_cases as bc  # noqa: E402
 import attention_cases as ac  # noqa: E402
+import attention_grad_cases as gc  # noqa: E402
 import softmax_cases as sc  # noqa: E402
 import sparse_amd  # noqa: E402
 from sparse_amd import _kernels as K  # noqa: E402
@@ -77,12 +80,22 @@ def main():
         ops = (q, k, v) if how == "numpy" else tuple(torch.from_numpy(x).to("cuda:0") for x in (q, k, v))
         if how == "strided":
             ops = tuple(strided(x) for x in ops)
-        out = sparse_amd.sparse_attention(s, *ops, scale=scale)
+        brng = np.random.default_rng([a.seed, case, 1])                     # (a stream of its own: the draws above stay as they were)
+        bias = None
+        if len(vals) and brng.random() < 0.5:                                # a bias in half of the cases: shared or per head, a fifth -inf
+            bias = bc.bias_of(int(brng.integers(1 << 30)), len(vals), dtype, None if brng.random() < 0.5 else lead,
+                              neg_inf=float(brng.choice([0.0, 0.2])))
+        order = gc.column_order(indptr, indices)[0] if layout == "csc" else slice(None)      # the caller's order of `s.data`
+        given = None if bias is None else np.ascontiguousarray(bias[..., order])
+        if given is not None and how != "numpy":
+            given = torch.from_numpy(given).to("cuda:0")
+        out = sparse_amd.sparse_attention(s, *ops, scale=scale, bias=given)
         out = out if isinstance(out, np.ndarray) else out.cpu().numpy()
-        want = ac.attention_heads(indptr, indices, vals, q, k, v, chunk, scale)
+        want = ac.attention_heads(indptr, indices, vals, q, k, v, chunk, scale) if bias is None else \
+            bc.attention_bias_heads(indptr, indices, vals, q, k, v, chunk, scale, bias)
         ok = sc.same_bits(out, want)
         print(f"case {case}: {np.dtype(dtype)} mask {np.dtype(mdt)} {np.dtype(idx)} {layout} {how} chunk {chunk} group {group} scale {scale} "
-              f"D {D} Dv {Dv} heads {lead} rows {len(lengths)} nnz {len(vals)} longest {max(lengths)}: {'same bits' if ok else 'DIFFERENT'}",
+              f"bias {None if bias is None else bias.shape} D {D} Dv {Dv} heads {lead} rows {len(lengths)} nnz {len(vals)} longest {max(lengths)}: {'same bits' if ok else 'DIFFERENT'}",
               flush=True)
         if not ok:
             raise SystemExit(1)

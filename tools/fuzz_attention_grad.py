@@ -7,8 +7,9 @@ A case draws: float32 | float64 operands, 32- | 64-bit indices, a chunk of 64 ..
 or Zipf lengths of up to 3000 - as the ROW lengths of the mask or, transposed, as its COLUMN lengths (hubs beyond the chunk
 among many short ones) -, a share of empty rows or columns, D and Dv of 1 .. 140, no head axis, three heads or 2 x 2, float,
 integer or boolean mask values, now and then a scale, a stored zero, an infinity or a NaN among the mask values - and the mask
-as a COO, a COO built unsorted, a CSR or a CSC; the operands as NumPy arrays, device tensors or row-strided device views.
-Prints one line per case; exits 1 at the first difference."""
+as a COO, a COO built unsorted, a CSR or a CSC; the operands as NumPy arrays, device tensors or row-strided device views; in
+half of the cases an additive bias, shared or per head, with -inf entries in some: dbias is then compared too, in the order of
+the array the caller holds.  Prints one line per case; exits 1 at the first difference."""
 import argparse
 import os
 import sys
@@ -19,6 +20,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import attention_bias_cases as bc  # noqa: E402
 import attention_cases as ac  # noqa: E402
 import attention_grad_cases as gc  # noqa: E402
 import softmax_cases as sc  # noqa: E402
@@ -84,13 +86,25 @@ def main():
         ops = (q, k, v, g) if how == "numpy" else tuple(torch.from_numpy(x).to("cuda:0") for x in (q, k, v, g))
         if how == "strided":
             ops = tuple(strided(x) for x in ops)
-        outs = sparse_amd.sparse_attention_grad(s, *ops, scale=scale)
+        brng = np.random.default_rng([a.seed, case, 1])                     # (a stream of its own: the draws above stay as they were)
+        bias = None
+        if len(vals) and brng.random() < 0.5:                                # a bias in half of the cases: shared or per head, a fifth -inf
+            bias = bc.bias_of(int(brng.integers(1 << 30)), len(vals), dtype, None if brng.random() < 0.5 else lead,
+                              neg_inf=float(brng.choice([0.0, 0.2])))
+        order = gc.column_order(indptr, indices)[0] if layout == "csc" else slice(None)      # the caller's order of `s.data`
+        given = None if bias is None else np.ascontiguousarray(bias[..., order])
+        if given is not None and how != "numpy":
+            given = torch.from_numpy(given).to("cuda:0")
+        outs = sparse_amd.sparse_attention_grad(s, *ops, scale=scale, bias=given)
         outs = [o if isinstance(o, np.ndarray) else o.cpu().numpy() for o in outs]
         want = gc.grad_heads(indptr, indices, vals, q, k, v, g, chunk, scale)
-        ok = all(sc.same_bits(o, w) for o, w in zip(outs, want))
+        if bias is not None:
+            want = bc.grad_bias_heads(indptr, indices, vals, q, k, v, g, chunk, scale, bias)
+            want = want[:3] + (want[3][..., order],)
+        ok = len(outs) == len(want) and all(sc.same_bits(o, w) for o, w in zip(outs, want))
         longest_col = int(np.bincount(np.asarray(indices, dtype=np.int64), minlength=1).max()) if len(vals) else 0
         print(f"case {case}: {np.dtype(dtype)} mask {np.dtype(mdt)} {np.dtype(idx)} {layout} {how} chunk {chunk} groups {group}/{col_group} "
-              f"scale {scale} D {D} Dv {Dv} heads {lead} shape {shape} nnz {len(vals)} longest row {int(np.diff(indptr).max())} "
+              f"scale {scale} bias {None if bias is None else bias.shape} D {D} Dv {Dv} heads {lead} shape {shape} nnz {len(vals)} longest row {int(np.diff(indptr).max())} "
               f"column {longest_col}: {'same bits' if ok else 'DIFFERENT'}", flush=True)
         if not ok:
             raise SystemExit(1)
