@@ -883,6 +883,23 @@ int spamd_softmax(int val_dtype, int idx_dtype, int64_t nseg, int64_t nnz, const
  *   spamd_attention; in a row of at most `chunk` elements a bias of -inf on the trailing elements gives the bits of the mask
  *   without them (fma(+0.0, v, acc) = acc for finite v).  bias == NULL is spamd_attention itself, bit for bit; bias_head < 0 is
  *   SPAMD_EINVAL.  The workspace is spamd_attention_ws_bytes: the long form parks the biased scores.
+ *   spamd_attention_dropout: the same (bias may be NULL) with dropout on the probabilities.  The keep decision of the stored
+ *   (CSR) position pos = s_ptr[r] + i of head h is word 0, x, of Philox4x32-10 (Salmon et al., Random123: multipliers
+ *   0xD2511F53 and 0xCD9E8D57, key increments 0x9E3779B9 and 0xBB67AE85) under the key (seed low 32 bits, seed high 32 bits)
+ *   of the counter (pos low, pos high, hn low, hn high), hn = head0 + h as a 64-bit value: keep_i iff x >= thr, thr =
+ *   (uint32) floor(rate * 2^32) computed in double (exact for 0 <= rate < 1; the drop probability is thr / 2^32).  It is a
+ *   function of (seed, hn, pos) alone: no state, no atomics, the same in every form and launch geometry; `seed` carries the
+ *   64 bits of the unsigned seed.  After p_i:
+ *     c     = (T)(1.0 / (1.0 - rate)), the division in double, rounded once to T
+ *     pd_i  = keep_i ? p_i * c : +0.0, one multiply
+ *   and out is the output loop above with pd_i in the place of p_i: a dropped element still takes part, as the value +0.0 (no
+ *   compaction).  NaN, infinity and a row whose elements are all dropped follow from the arithmetic; such a row is +0.0 for
+ *   finite v.  rate == 0 gives the bits of spamd_attention / spamd_attention_bias (their kernels run).  rate outside [0, 1)
+ *   or NaN, or head0 < 0, is SPAMD_EINVAL before any launch; every other argument rule is spamd_attention_bias's.  The
+ *   workspace is spamd_attention_ws_bytes.
+ *   spamd_attention_keep: the decisions by themselves, from the same device code: out[h * nnz + p] = 1 when position pos0 + p
+ *   of head head0 + h is kept, else 0, for h < H, p < nnz.  Negative nnz, H, pos0 or head0, a rate outside [0, 1), or a null
+ *   out with work to do is SPAMD_EINVAL.
  * ------------------------------------------------------------------------------------- */
 int64_t spamd_attention_ws_bytes(int val_dtype, int64_t nnz, int64_t H, int64_t Dv, int64_t chunk);
 int spamd_attention(int val_dtype, int idx_dtype, int64_t M, int64_t N, int64_t nnz, int64_t H, int64_t D, int64_t Dv,
@@ -895,6 +912,14 @@ int spamd_attention_bias(int val_dtype, int idx_dtype, int64_t M, int64_t N, int
                          const void* k, int64_t k_pitch, int64_t k_head, const void* v, int64_t v_pitch, int64_t v_head,
                          int has_scale, double scale, int group, int64_t short_max, int64_t chunk, int64_t max_len,
                          const void* bias, int64_t bias_head, void* ws, int64_t ws_bytes, void* out, void* stream);
+int spamd_attention_dropout(int val_dtype, int idx_dtype, int64_t M, int64_t N, int64_t nnz, int64_t H, int64_t D, int64_t Dv,
+                            const void* s_ptr, const void* s_idx, const void* s_val, const void* q, int64_t q_pitch,
+                            int64_t q_head, const void* k, int64_t k_pitch, int64_t k_head, const void* v, int64_t v_pitch,
+                            int64_t v_head, int has_scale, double scale, int group, int64_t short_max, int64_t chunk,
+                            int64_t max_len, const void* bias, int64_t bias_head, double rate, int64_t seed, int64_t head0,
+                            void* ws, int64_t ws_bytes, void* out, void* stream);
+int spamd_attention_keep(int64_t nnz, int64_t H, int64_t pos0, int64_t head0, double rate, int64_t seed, uint8_t* out,
+                         void* stream);
 
 /* =======================================================================================
  * A16 the backward pass of sparse attention (csrc/attention_grad.hip): from g = d loss / d out (H, M, Dv) of A15, for every
@@ -946,6 +971,15 @@ int spamd_attention_bias(int val_dtype, int idx_dtype, int64_t M, int64_t N, int
  *   as independent of group / col_group / short_max / max_row / max_col as dq.  dbias == NULL skips the store.  bias == NULL
  *   is spamd_attention_grad itself, bit for bit, and dbias is then not written; bias_head < 0 is SPAMD_EINVAL.  The
  *   workspace is spamd_attention_grad_ws_bytes.
+ *   spamd_attention_grad_dropout: the backward pass of spamd_attention_dropout (bias and dbias may be NULL).  rate, seed and
+ *   head0 are as there; t_i and p_i are the forward's, keep_i is recomputed from (seed, head0 + h, pos), c and pd_i are as
+ *   there.  In the row pass
+ *     ed_i  = keep_i ? e_i * c : +0.0, one multiply
+ *     u_i   = p_i * ed_i;  delta as above over these u_i;  z_i = p_i * (ed_i - delta)
+ *   and y_i, dq and dbias = z_i follow as above.  The row pass parks pd_i, not p_i, so the column pass is unchanged: dv takes
+ *   fma(pd[pos_i], g[r_i][j], acc) and dk takes y.  rate == 0 gives the bits of spamd_attention_grad /
+ *   spamd_attention_grad_bias (their kernels run).  rate outside [0, 1) or NaN, or head0 < 0, is SPAMD_EINVAL before any
+ *   launch; every other argument rule is spamd_attention_grad_bias's.
  * ------------------------------------------------------------------------------------- */
 int64_t spamd_attention_grad_ws_bytes(int val_dtype, int64_t nnz, int64_t H, int64_t D, int64_t Dv, int64_t chunk);
 int spamd_attention_grad(int val_dtype, int idx_dtype, int64_t M, int64_t N, int64_t nnz, int64_t H, int64_t D, int64_t Dv,
@@ -962,6 +996,14 @@ int spamd_attention_grad_bias(int val_dtype, int idx_dtype, int64_t M, int64_t N
                               int64_t g_head, int has_scale, double scale, int group, int col_group, int64_t short_max,
                               int64_t chunk, int64_t max_row, int64_t max_col, const void* bias, int64_t bias_head, void* dbias,
                               void* ws, int64_t ws_bytes, void* dq, void* dk, void* dv, void* stream);
+int spamd_attention_grad_dropout(int val_dtype, int idx_dtype, int64_t M, int64_t N, int64_t nnz, int64_t H, int64_t D, int64_t Dv,
+                                 const void* s_ptr, const void* s_idx, const void* s_val, const void* c_ptr,
+                                 const int64_t* c_perm, const void* c_row, const void* q, int64_t q_pitch, int64_t q_head,
+                                 const void* k, int64_t k_pitch, int64_t k_head, const void* v, int64_t v_pitch, int64_t v_head,
+                                 const void* g, int64_t g_pitch, int64_t g_head, int has_scale, double scale, int group,
+                                 int col_group, int64_t short_max, int64_t chunk, int64_t max_row, int64_t max_col,
+                                 const void* bias, int64_t bias_head, void* dbias, double rate, int64_t seed, int64_t head0,
+                                 void* ws, int64_t ws_bytes, void* dq, void* dk, void* dv, void* stream);
 
 #ifdef __cplusplus
 }

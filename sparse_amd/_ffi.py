@@ -180,6 +180,14 @@ SIGNATURES = {
                                _vp, _i64, _i64, _int, _C.c_double, _int, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
     "spamd_attention_bias": (_int, [_int, _int, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64,
                                     _vp, _i64, _i64, _int, _C.c_double, _int, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "spamd_attention_dropout": (_int, [_int, _int, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64,
+                                       _vp, _i64, _i64, _int, _C.c_double, _int, _i64, _i64, _i64, _vp, _i64, _C.c_double, _i64, _i64,
+                                       _vp, _i64, _vp, _vp]),
+    "spamd_attention_keep": (_int, [_i64, _i64, _i64, _i64, _C.c_double, _i64, _vp, _vp]),
+    "spamd_attention_grad_dropout": (_int, [_int, _int, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                            _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _int, _C.c_double, _int, _int,
+                                            _i64, _i64, _i64, _i64, _vp, _i64, _vp, _C.c_double, _i64, _i64, _vp, _i64, _vp, _vp, _vp,
+                                            _vp]),
     "spamd_attention_grad_bias": (_int, [_int, _int, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
                                          _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _int, _C.c_double, _int, _int, _i64,
                                          _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),

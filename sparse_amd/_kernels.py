@@ -1765,8 +1765,36 @@ def _bias2(bias, lead, H, nnz, dt, what):
     return b2, (int(b2.stride(0)) if H > 1 else 0)
 
 
+def _dropout_args(dropout, seed, what):
+    """(rate, the 64 bits of the seed as a signed integer) of a kernel-level dropout, or None for no dropout (None or 0: the
+    seed is then ignored)"""
+    if dropout is None or float(dropout) == 0.0:
+        return None
+    rate = float(dropout)
+    if not 0.0 <= rate < 1.0:
+        raise ValueError(f"{what}: the dropout must lie in [0, 1), got {dropout!r}")
+    if seed is None:
+        raise ValueError(f"{what}: a dropout above 0 needs a seed (there is no hidden generator)")
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"{what}: the seed must lie in [0, 2^64), got {seed}")
+    return rate, seed - (1 << 64) if seed >= 1 << 63 else seed
+
+
+def attention_keep(nnz, heads, dropout, seed, device, *, pos0=0, head0=0):
+    """bool [heads, nnz]: the keep decisions of attention dropout for the stored (CSR) positions pos0 .. pos0 + nnz - 1 of the
+    heads head0 .. head0 + heads - 1 (spamd_attention_keep: the device code the attention kernels call)"""
+    nnz, heads = int(nnz), int(heads)
+    out = torch.empty((heads, nnz), dtype=torch.uint8, device=device)
+    require_hip(out)
+    dz = _dropout_args(dropout, seed, "attention_keep")
+    rate, sd = (0.0, 0) if dz is None else dz
+    _ffi.call("spamd_attention_keep", nnz, heads, int(pos0), int(head0), rate, sd, ptr(out), stream_ptr(out.device))
+    return out.view(torch.bool)
+
+
 def attention_rows(indptr, indices, svals, q, k, v, max_len, *, scale=None, group=None, chunk=None, form=None, short_max=None,
-                   bias=None):
+                   bias=None, dropout=None, seed=None):
     """out[h] = softmax_over_stored(scale * (s * (q[h] @ k[h].T))) @ v[h] for the CSR mask (`svals`, `indices`, `indptr`: M + 1
     int32 | int64 pointers) (spamd_attention).  `q` [..., M, D], `k` [..., N, D], `v` [..., N, Dv] are device tensors of the
     type of `svals` (float32 or float64) with the same leading axes; `max_len` is the longest row's length.  Returns the
@@ -1774,8 +1802,11 @@ def attention_rows(indptr, indices, svals, q, k, v, max_len, *, scale=None, grou
     row has at most 64 elements), "wide" (a wave per row; at most `chunk` elements), "long" (a wave per row up to `chunk`,
     default 64 here, pieces beyond); `short_max` moves the length at which a row goes from a sub-group to a wave (sweeps).
     `bias`: None, or a device tensor of that type in the order of `svals`, [nnz] (every head shares it) or [..., nnz], added to
-    the scores after the scale (spamd_attention_bias)."""
+    the scores after the scale (spamd_attention_bias).  `dropout`: None, or a rate in [0, 1) with a `seed` in [0, 2^64): the
+    probabilities are dropped and rescaled by the counter-based decision of (seed, head, stored position)
+    (spamd_attention_dropout); None or 0 reaches the entries without it."""
     dev = require_hip(indptr, indices, svals, q, k, v)
+    dz = _dropout_args(dropout, seed, "attention")
     dt = svals.dtype
     if dt not in (torch.float32, torch.float64) or any(t.dtype != dt for t in (q, k, v)):
         raise TypeError("attention: the mask values, q, k and v must all be float32 or all float64")
@@ -1806,6 +1837,15 @@ def attention_rows(indptr, indices, svals, q, k, v, max_len, *, scale=None, grou
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
     has_scale = scale is not None
     sc = float(np.asarray(scale).astype(np_dtype(dt))) if has_scale else 0.0
+    if dz is not None:
+        b2, bh = (None, 0) if bias is None else _bias2(bias, lead, H, nnz, dt, "attention")
+        if bias is not None:
+            require_hip(indptr, bias)
+        _ffi.call("spamd_attention_dropout", code_of(dt), code_of(indptr.dtype), M, N, nnz, H, D, Dv, ptr(indptr.contiguous()),
+                  ptr(indices.contiguous()), ptr(svals.contiguous()), ptr(q3), qp, qh, ptr(k3), kp, kh, ptr(v3), vp, vh,
+                  int(has_scale), sc, group, short_max, chunk, max_len, ptr(b2), bh, dz[0], dz[1], 0, ptr(ws), ws_bytes, ptr(out),
+                  stream_ptr(dev))
+        return out
     if bias is None:
         _ffi.call("spamd_attention", code_of(dt), code_of(indptr.dtype), M, N, nnz, H, D, Dv, ptr(indptr.contiguous()),
                   ptr(indices.contiguous()), ptr(svals.contiguous()), ptr(q3), qp, qh, ptr(k3), kp, kh, ptr(v3), vp, vh,
@@ -1851,7 +1891,8 @@ def attention_grad_chunk():
 
 
 def attention_grad_rows(indptr, indices, svals, colptr, colperm, colrows, q, k, v, g, max_row, max_col, *, scale=None, group=None,
-                        col_group=None, chunk=None, form=None, short_max=None, bias=None, want_dbias=False):
+                        col_group=None, chunk=None, form=None, short_max=None, bias=None, want_dbias=False, dropout=None,
+                        seed=None):
     """(dq, dk, dv) of `attention_rows` for the gradient `g` [..., M, Dv] of its result (spamd_attention_grad).  With a `bias`
     (as in `attention_rows`: spamd_attention_grad_bias) the probabilities are the biased forward's and the result is
     (dq, dk, dv, dbias): dbias [..., nnz] in the order of `svals`, always per head, or None unless `want_dbias`.  The mask and
@@ -1860,8 +1901,10 @@ def attention_grad_rows(indptr, indices, svals, colptr, colperm, colrows, q, k, 
     `max_col` the longest row and column.  `form` forces a kernel form on BOTH passes, for tests and sweeps: "short"
     (sub-groups of `group` / `col_group` lanes; at most 64 elements a row and a column), "wide" (a wave each; at most `chunk`),
     "long" (a wave up to `chunk`, default 64 here, pieces beyond); `short_max` moves the length at which a row or column goes
-    from a sub-group to a wave (sweeps)."""
+    from a sub-group to a wave (sweeps).  `dropout` and `seed` are those of `attention_rows`: the decisions are recomputed, so
+    the backward drops what the forward dropped (spamd_attention_grad_dropout); None or 0 reaches the entries without it."""
     dev = require_hip(indptr, indices, svals, colptr, colperm, colrows, q, k, v, g)
+    dz = _dropout_args(dropout, seed, "attention_grad")
     dt = svals.dtype
     if dt not in (torch.float32, torch.float64) or any(t.dtype != dt for t in (q, k, v, g)):
         raise TypeError("attention_grad: the mask values, q, k, v and g must all be float32 or all float64")
@@ -1898,6 +1941,19 @@ def attention_grad_rows(indptr, indices, svals, colptr, colperm, colrows, q, k, 
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
     has_scale = scale is not None
     sc = float(np.asarray(scale).astype(np_dtype(dt))) if has_scale else 0.0
+    if dz is not None:
+        b2, bh = (None, 0) if bias is None else _bias2(bias, lead, H, nnz, dt, "attention_grad")
+        if bias is not None:
+            require_hip(indptr, bias)
+        dbias = None
+        if bias is not None and want_dbias:
+            dbias = (torch.zeros if D == 0 and Dv == 0 else torch.empty)(lead + (nnz,), dtype=dt, device=dev)
+        _ffi.call("spamd_attention_grad_dropout", code_of(dt), code_of(indptr.dtype), M, N, nnz, H, D, Dv, ptr(indptr.contiguous()),
+                  ptr(indices.contiguous()), ptr(svals.contiguous()), ptr(colptr.contiguous()), ptr(colperm.contiguous()),
+                  ptr(colrows.contiguous()), ptr(q3), qp, qh, ptr(k3), kp, kh, ptr(v3), vp, vh, ptr(g3), gp, gh, int(has_scale), sc,
+                  group, col_group, short_max, chunk, max_row, max_col, ptr(b2), bh, ptr(dbias), dz[0], dz[1], 0, ptr(ws), ws_bytes,
+                  ptr(dq), ptr(dk), ptr(dv), stream_ptr(dev))
+        return (dq, dk, dv) if bias is None else (dq, dk, dv, dbias)
     if bias is None:
         _ffi.call("spamd_attention_grad", code_of(dt), code_of(indptr.dtype), M, N, nnz, H, D, Dv, ptr(indptr.contiguous()),
                   ptr(indices.contiguous()), ptr(svals.contiguous()), ptr(colptr.contiguous()), ptr(colperm.contiguous()),

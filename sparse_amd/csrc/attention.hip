@@ -10,6 +10,8 @@
 //   t_i  = s_i * w_i (one multiply);  t_i = scale * t_i (one more) when a scale is given;  t_i = t_i + b_i (one add, after the
 //          scale) when a bias is given (spamd_attention_bias; B of AtBias<T, B>: the kernels without one compile as before it existed)
 //   p_i  = A14's softmax of t_0 .. t_{n-1} (maximum first, exp_det, 64 accumulators per piece of `chunk`, one division)
+//   pd_i = keep_i ? p_i * c : +0.0 with dropout (spamd_attention_dropout; P of AtDrop<T, P>, csrc/attention_dropout.h): c =
+//          (T)(1 / (1 - rate)), keep_i from (seed, head, stored position); it takes the place of p_i below, a dropped element as +0.0
 //   out[r, j]: the elements are cut into pieces of `chunk`; a piece starts at +0.0 and takes acc = fma(p_i, v[c_i, j], acc) for
 //          i ascending; the piece sums are added in piece order (the first piece's sum is the start).  An empty row is +0.0.
 // No atomics; every output is written once; neither `group`, `short_max`, `max_len` nor the launch geometry changes a bit.
@@ -25,6 +27,7 @@
 //          Six launches that each END before the next reads what it wrote: piece scores and maxima, row maxima, piece sums,
 //          row sums (piece order), piece outputs, row outputs (piece order).
 #include "attention_common.h"
+#include "attention_dropout.h"
 #include "exp_det.h"
 
 namespace spamd {
@@ -51,10 +54,13 @@ struct AtIn {
 };
 
 // ---- short: a sub-group of G lanes per (row, head) ----------------------------------------------------------------------------
-template <typename T, typename I, int G, bool B>
+// (P: with dropout - spamd_attention_dropout; P = false compiles as before it existed, AtDrop<T, false> being an empty argument)
+template <typename T, typename I, int G, bool B, bool P>
 __global__ void __launch_bounds__(256)
-at_short_kernel(AtIn<T, I> in, int64_t short_max, AtBias<T, B> bz) {
+at_short_kernel(AtIn<T, I> in, int64_t short_max, AtMods<T, B, P> mz) {
 #pragma clang fp contract(off)
+  const AtBias<T, B>& bz = mz;
+  const AtDrop<T, P>& dz = mz;
   constexpr int V = 64 / G;
   constexpr int GPB = 256 / G;
   const int sub = threadIdx.x % G;
@@ -118,6 +124,11 @@ at_short_kernel(AtIn<T, I> in, int64_t short_max, AtBias<T, B> bz) {
       const T s = at_xsum<T, G>(a[0]);
 #pragma unroll
       for (int r = 0; r < V; ++r) t[r] = t[r] / s;
+      if constexpr (P) {   // pd_i = keep_i ? p_i * c : +0.0: t holds pd from here on
+#pragma unroll
+        for (int r = 0; r < V; ++r)
+          if (sub + r * G < n) t[r] = dz.mul(dz.keep(head, b + sub + r * G), t[r]);
+      }
       // phase 3: the output row, 64 columns at a time (lane u: the columns u, u + G, ..), four v rows in flight
       T* __restrict__ orow = in.out + (head * in.M + row) * in.Dv;
       for (int jb = 0; jb < in.Dv; jb += 64) {
@@ -151,10 +162,12 @@ at_short_kernel(AtIn<T, I> in, int64_t short_max, AtBias<T, B> bz) {
 }
 
 // ---- wide: a wave (one workgroup) per (row, head), the scores in LDS ------------------------------------------------------------
-template <typename T, typename I, bool B>
+template <typename T, typename I, bool B, bool P>
 __global__ void __launch_bounds__(64)
-at_wide_kernel(AtIn<T, I> in, int64_t above, int64_t upto, AtBias<T, B> bz) {
+at_wide_kernel(AtIn<T, I> in, int64_t above, int64_t upto, AtMods<T, B, P> mz) {
 #pragma clang fp contract(off)
+  const AtBias<T, B>& bz = mz;
+  const AtDrop<T, P>& dz = mz;
   extern __shared__ __attribute__((aligned(16))) unsigned char at_smem[];
   T* __restrict__ lds = reinterpret_cast<T*>(at_smem);   // `upto` values
   const int lane = threadIdx.x;
@@ -201,7 +214,7 @@ at_wide_kernel(AtIn<T, I> in, int64_t above, int64_t upto, AtBias<T, B> bz) {
           acc = acc + e;
         }
         const T s = at_xsum<T, 64>(acc);
-        for (int x = lane; x < n; x += 64) lds[x] = lds[x] / s;
+        for (int x = lane; x < n; x += 64) lds[x] = dz.mul(dz.keep(head, b + x), lds[x] / s);
         __syncthreads();
         T* __restrict__ orow = in.out + (head * in.M + row) * in.Dv;
         for (int jb = 0; jb < in.Dv; jb += 64) {
@@ -223,8 +236,8 @@ __host__ __device__ __forceinline__ int64_t at_ws_values(int64_t nnz, int64_t nw
   return nnz + 8 * nwin + 2 * nwin * Dv;
 }
 
-template <typename T, typename I, int PHASE, bool B>
-__device__ __forceinline__ void at_piece(const AtIn<T, I>& in, const AtBias<T, B>& bz, int64_t head, int64_t row, int64_t b, int64_t s, int64_t e,
+template <typename T, typename I, int PHASE, bool B, bool P>
+__device__ __forceinline__ void at_piece(const AtIn<T, I>& in, const AtBias<T, B>& bz, const AtDrop<T, P>& dz, int64_t head, int64_t row, int64_t b, int64_t s, int64_t e,
                                          int64_t chunk, int64_t nnz, int64_t nwin, int lane, T* __restrict__ ws) {
 #pragma clang fp contract(off)
   T* __restrict__ sc = ws;
@@ -269,7 +282,7 @@ __device__ __forceinline__ void at_piece(const AtIn<T, I>& in, const AtBias<T, B
         T p = T(0);
         int64_t c = 0;
         if (lane < cnt) {
-          p = exp_det(sc[x0 + lane] - m) / sum;
+          p = dz.mul(dz.keep(head, x0 + lane), exp_det(sc[x0 + lane] - m) / sum);   // (the decision is made here, where the piece outputs are formed)
           c = (int64_t)in.idx[x0 + lane];
         }
         for (int i = 0; i < cnt; i += 4) {
@@ -290,9 +303,12 @@ __device__ __forceinline__ void at_piece(const AtIn<T, I>& in, const AtBias<T, B
   }
 }
 
-template <typename T, typename I, int PHASE, bool B>
+// (P: the piece outputs, PHASE 2, with dropout; the scores, maxima and sums before them do not see it)
+template <typename T, typename I, int PHASE, bool B, bool P>
 __global__ void __launch_bounds__(256)
-at_piece_kernel(AtIn<T, I> in, int64_t nnz, int64_t chunk, int64_t nwin, T* __restrict__ ws_all, AtBias<T, B> bz) {
+at_piece_kernel(AtIn<T, I> in, int64_t nnz, int64_t chunk, int64_t nwin, T* __restrict__ ws_all, AtMods<T, B, P> mz) {
+  const AtBias<T, B>& bz = mz;
+  const AtDrop<T, P>& dz = mz;
   const int lane = threadIdx.x & 63;
   const int64_t M = in.M;
   {
@@ -307,13 +323,13 @@ at_piece_kernel(AtIn<T, I> in, int64_t nnz, int64_t chunk, int64_t nwin, T* __re
         if (e0 - b0 > chunk) {
           const int64_t s = b0 + (lo - b0 + chunk - 1) / chunk * chunk;   // the one piece start of this row in [lo, lo + chunk)
           if (s < hi && s < e0)
-            at_piece<T, I, PHASE, B>(in, bz, head, r0, b0, s, s + chunk < e0 ? s + chunk : e0, chunk, nnz, nwin, lane, ws);
+            at_piece<T, I, PHASE, B, P>(in, bz, dz, head, r0, b0, s, s + chunk < e0 ? s + chunk : e0, chunk, nnz, nwin, lane, ws);
         }
       }
       const int64_t r1 = at_row_of(in.ptr, M, hi - 1);
       if (r1 > r0) {   // starts inside the window; only the last such row can be longer than the window
         const int64_t b1 = (int64_t)in.ptr[r1], e1 = (int64_t)in.ptr[r1 + 1];
-        if (e1 - b1 > chunk) at_piece<T, I, PHASE, B>(in, bz, head, r1, b1, b1, b1 + chunk, chunk, nnz, nwin, lane, ws);
+        if (e1 - b1 > chunk) at_piece<T, I, PHASE, B, P>(in, bz, dz, head, r1, b1, b1, b1 + chunk, chunk, nnz, nwin, lane, ws);
       }
     }
   }
@@ -378,13 +394,13 @@ static unsigned at_grid(int64_t items, int64_t per_block) {
   return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(items, per_block), (int64_t)1 << 20));
 }
 
-template <typename T, typename I, bool B>
-static int attention_typed(AtIn<T, I> in, AtBias<T, B> bz, int64_t nnz, int group, int64_t short_max, int64_t chunk, int64_t max_len, void* ws_,
-                           hipStream_t st) {
+template <typename T, typename I, bool B, bool P>
+static int attention_typed(AtIn<T, I> in, AtBias<T, B> bz, AtDrop<T, P> dz, int64_t nnz, int group, int64_t short_max, int64_t chunk,
+                           int64_t max_len, void* ws_, hipStream_t st) {
   const unsigned gy = (unsigned)in.H;
   {   // (always: the rows without a stored element are written here)
 #define AT_SHORT(G) \
-  hipLaunchKernelGGL((at_short_kernel<T, I, G, B>), dim3(at_grid(in.M, 256 / G), gy), dim3(256), 0, st, in, short_max, bz)
+  hipLaunchKernelGGL((at_short_kernel<T, I, G, B, P>), dim3(at_grid(in.M, 256 / G), gy), dim3(256), 0, st, in, short_max, AtMods<T, B, P>(bz, dz))
     if (group == 8) AT_SHORT(8);
     else if (group == 16) AT_SHORT(16);
     else if (group == 32) AT_SHORT(32);
@@ -393,8 +409,8 @@ static int attention_typed(AtIn<T, I> in, AtBias<T, B> bz, int64_t nnz, int grou
     if (int rc = launch_status()) return rc;
   }
   if (std::min(max_len, chunk) > short_max) {
-    hipLaunchKernelGGL((at_wide_kernel<T, I, B>), dim3(at_grid(in.M, 64), gy), dim3(64), (size_t)chunk * sizeof(T), st, in, short_max,
-                       chunk, bz);
+    hipLaunchKernelGGL((at_wide_kernel<T, I, B, P>), dim3(at_grid(in.M, 64), gy), dim3(64), (size_t)chunk * sizeof(T), st, in, short_max,
+                       chunk, AtMods<T, B, P>(bz, dz));
     if (int rc = launch_status()) return rc;
   }
   if (max_len > chunk) {
@@ -402,15 +418,16 @@ static int attention_typed(AtIn<T, I> in, AtBias<T, B> bz, int64_t nnz, int grou
     const int64_t nwin = ceil_div(nnz, chunk);
     const dim3 pg(at_grid(nwin, 4), gy), jg(at_grid(in.M, 256), gy);
     const AtBias<T, false> nob{};   // the biased scores are in the workspace from here on
-    hipLaunchKernelGGL((at_piece_kernel<T, I, 0, B>), pg, dim3(256), 0, st, in, nnz, chunk, nwin, ws, bz);
+    const AtDrop<T, false> nod{};   // only the piece outputs see dropout
+    hipLaunchKernelGGL((at_piece_kernel<T, I, 0, B, false>), pg, dim3(256), 0, st, in, nnz, chunk, nwin, ws, AtMods<T, B, false>(bz, nod));
     if (int rc = launch_status()) return rc;
     hipLaunchKernelGGL((at_join_kernel<T, I, 0>), jg, dim3(256), 0, st, in, nnz, chunk, nwin, ws);
     if (int rc = launch_status()) return rc;
-    hipLaunchKernelGGL((at_piece_kernel<T, I, 1, false>), pg, dim3(256), 0, st, in, nnz, chunk, nwin, ws, nob);
+    hipLaunchKernelGGL((at_piece_kernel<T, I, 1, false, false>), pg, dim3(256), 0, st, in, nnz, chunk, nwin, ws, AtMods<T, false, false>(nob, nod));
     if (int rc = launch_status()) return rc;
     hipLaunchKernelGGL((at_join_kernel<T, I, 1>), jg, dim3(256), 0, st, in, nnz, chunk, nwin, ws);
     if (int rc = launch_status()) return rc;
-    hipLaunchKernelGGL((at_piece_kernel<T, I, 2, false>), pg, dim3(256), 0, st, in, nnz, chunk, nwin, ws, nob);
+    hipLaunchKernelGGL((at_piece_kernel<T, I, 2, false, P>), pg, dim3(256), 0, st, in, nnz, chunk, nwin, ws, AtMods<T, false, P>(nob, dz));
     if (int rc = launch_status()) return rc;
     hipLaunchKernelGGL((at_join_kernel<T, I, 2>), jg, dim3(256), 0, st, in, nnz, chunk, nwin, ws);
     if (int rc = launch_status()) return rc;
@@ -418,24 +435,54 @@ static int attention_typed(AtIn<T, I> in, AtBias<T, B> bz, int64_t nnz, int grou
   return 0;
 }
 
+struct AtArgs {
+  int64_t M, nnz, H, D, Dv;
+  const void *ptr, *idx, *sv, *q, *k, *v;
+  int64_t qp, qh, kp, kh, vp, vh;
+  int has_scale;
+  double scale;
+  int group;
+  int64_t short_max, chunk, max_len;
+  const void* bias;
+  int64_t bias_head;
+  double rate;   // 0: no dropout - the kernels of spamd_attention / spamd_attention_bias
+  uint64_t seed;
+  int64_t head0;
+  void *ws, *out;
+};
+
 template <typename T, typename I>
-static int attention_in(int64_t M, int64_t nnz, int64_t H, int64_t D, int64_t Dv, const void* ptr, const void* idx, const void* sv,
-                        const void* q, int64_t qp, int64_t qh, const void* k, int64_t kp, int64_t kh, const void* v, int64_t vp,
-                        int64_t vh, int has_scale, double scale, int group, int64_t short_max, int64_t chunk, int64_t max_len,
-                        const void* bias, int64_t bias_head, void* ws, void* out, hipStream_t st) {
-  const int64_t ws_head = max_len > chunk ? at_ws_values(nnz, ceil_div(nnz, chunk), Dv) : 0;
-  for (int64_t h0 = 0; h0 < H; h0 += 65535) {   // a head per grid.y: at most 65535 of them in one launch
-    AtIn<T, I> in{(const I*)ptr, (const I*)idx, (const T*)sv, (const T*)q + h0 * qh, (const T*)k + h0 * kh, (const T*)v + h0 * vh,
-                  qp, qh, kp, kh, vp, vh, M, std::min<int64_t>(H - h0, 65535), (int)D, (int)Dv, (T)scale, has_scale != 0,
-                  (T*)out + h0 * M * Dv};
-    T* wsh = ws ? (T*)ws + h0 * ws_head : nullptr;
+static int attention_in(const AtArgs& a, hipStream_t st) {
+  const int64_t ws_head = a.max_len > a.chunk ? at_ws_values(a.nnz, ceil_div(a.nnz, a.chunk), a.Dv) : 0;
+  for (int64_t h0 = 0; h0 < a.H; h0 += 65535) {   // a head per grid.y: at most 65535 of them in one launch
+    AtIn<T, I> in{(const I*)a.ptr, (const I*)a.idx, (const T*)a.sv, (const T*)a.q + h0 * a.qh, (const T*)a.k + h0 * a.kh,
+                  (const T*)a.v + h0 * a.vh, a.qp, a.qh, a.kp, a.kh, a.vp, a.vh, a.M, std::min<int64_t>(a.H - h0, 65535), (int)a.D,
+                  (int)a.Dv, (T)a.scale, a.has_scale != 0, (T*)a.out + h0 * a.M * a.Dv};
+    T* wsh = a.ws ? (T*)a.ws + h0 * ws_head : nullptr;
+    const AtBias<T, true> bz{(const T*)a.bias + h0 * a.bias_head, a.bias_head, nullptr};
+    // (the head's number goes on across the launches: head 65535 does not repeat head 0's decisions)
+    const AtDrop<T, true> dz{a.seed, (uint64_t)a.head0 + (uint64_t)h0, dropout_threshold(a.rate), (T)(1.0 / (1.0 - a.rate))};
     int rc;
-    if (bias) rc = attention_typed<T, I, true>(in, AtBias<T, true>{(const T*)bias + h0 * bias_head, bias_head, nullptr}, nnz, group,
-                                               short_max, chunk, max_len, wsh, st);
-    else rc = attention_typed<T, I, false>(in, AtBias<T, false>{}, nnz, group, short_max, chunk, max_len, wsh, st);
+    if (a.rate > 0.0) {
+      if (a.bias) rc = attention_typed<T, I, true, true>(in, bz, dz, a.nnz, a.group, a.short_max, a.chunk, a.max_len, wsh, st);
+      else rc = attention_typed<T, I, false, true>(in, AtBias<T, false>{}, dz, a.nnz, a.group, a.short_max, a.chunk, a.max_len, wsh, st);
+    } else {
+      const AtDrop<T, false> nod{};
+      if (a.bias) rc = attention_typed<T, I, true, false>(in, bz, nod, a.nnz, a.group, a.short_max, a.chunk, a.max_len, wsh, st);
+      else rc = attention_typed<T, I, false, false>(in, AtBias<T, false>{}, nod, a.nnz, a.group, a.short_max, a.chunk, a.max_len, wsh, st);
+    }
     if (rc) return rc;
   }
   return 0;
+}
+
+// out[h * nnz + p] = keep(seed, head0 + h, pos0 + p): the decisions by themselves (spamd_attention_keep)
+__global__ void __launch_bounds__(256)
+at_keep_kernel(int64_t nnz, int64_t total, uint64_t pos0, uint64_t head0, uint64_t seed, uint32_t thr, uint8_t* __restrict__ out) {
+  for (int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x; x < total; x += (int64_t)gridDim.x * 256) {
+    const int64_t h = x / nnz, p = x - h * nnz;
+    out[x] = dropout_keep(seed, head0 + (uint64_t)h, pos0 + (uint64_t)p, thr) ? 1 : 0;
+  }
 }
 
 }  // namespace spamd
@@ -450,6 +497,38 @@ extern "C" int64_t spamd_attention_ws_bytes(int val_dtype, int64_t nnz, int64_t 
   return H * at_ws_values(nnz, ceil_div(nnz, chunk), Dv) * esz;
 }
 
+// the entry with dropout on the probabilities: pd_i = keep_i ? p_i * c : +0.0 takes the place of p_i in the output loop, c =
+// (T)(1 / (1 - rate)), keep_i decided by csrc/attention_dropout.h from (seed, head0 + head, stored position).  rate = 0 is
+// spamd_attention_bias (the same kernels); bias = NULL is no bias.  The workspace is that of spamd_attention_ws_bytes
+extern "C" int spamd_attention_dropout(int val_dtype, int idx_dtype, int64_t M, int64_t N, int64_t nnz, int64_t H, int64_t D, int64_t Dv,
+                                       const void* s_ptr, const void* s_idx, const void* s_val, const void* q, int64_t q_pitch,
+                                       int64_t q_head, const void* k, int64_t k_pitch, int64_t k_head, const void* v, int64_t v_pitch,
+                                       int64_t v_head, int has_scale, double scale, int group, int64_t short_max, int64_t chunk,
+                                       int64_t max_len, const void* bias, int64_t bias_head, double rate, int64_t seed, int64_t head0,
+                                       void* ws, int64_t ws_bytes, void* out, void* stream) {
+  if (val_dtype != SPAMD_F32 && val_dtype != SPAMD_F64) return SPAMD_ETYPE;
+  if (idx_dtype != SPAMD_I32 && idx_dtype != SPAMD_I64) return SPAMD_ETYPE;
+  if (M < 0 || N < 0 || nnz < 0 || H < 0 || D < 0 || Dv < 0 || max_len < 0 || max_len > nnz) return SPAMD_EINVAL;
+  if (D > INT32_MAX - 128 || Dv > INT32_MAX - 128) return SPAMD_EINVAL;   // (row widths are 32-bit in the kernels)
+  if (q_pitch < 0 || q_head < 0 || k_pitch < 0 || k_head < 0 || v_pitch < 0 || v_head < 0) return SPAMD_EINVAL;
+  if (bias_head < 0) return SPAMD_EINVAL;
+  if (!dropout_rate_ok(rate) || head0 < 0) return SPAMD_EINVAL;
+  if (group != 8 && group != 16 && group != 32 && group != 64) return SPAMD_EINVAL;
+  if (chunk < 64 || chunk > ATTENTION_MAX_CHUNK || chunk % 64 || short_max < 0 || short_max > 64) return SPAMD_EINVAL;
+  if (M == 0 || H == 0 || Dv == 0) return 0;
+  if (!out || !s_ptr) return SPAMD_EINVAL;
+  if (nnz > 0 && (!s_idx || !s_val || !k || !v || (D > 0 && !q))) return SPAMD_EINVAL;
+  if (max_len > chunk && (!ws || ws_bytes < spamd_attention_ws_bytes(val_dtype, nnz, H, Dv, chunk))) return SPAMD_EWS;
+  const AtArgs a{M, nnz, H, D, Dv, s_ptr, s_idx, s_val, q, k, v, q_pitch, q_head, k_pitch, k_head, v_pitch, v_head, has_scale, scale,
+                 group, short_max, chunk, max_len, bias, bias_head, rate, (uint64_t)seed, head0, ws, out};
+  hipStream_t st = (hipStream_t)stream;
+  SPAMD_DISPATCH_IDX(idx_dtype, I, {
+    if (val_dtype == SPAMD_F32) return attention_in<float, I>(a, st);
+    return attention_in<double, I>(a, st);
+  })
+  return SPAMD_ETYPE;
+}
+
 // the entry with an additive bias: b[head * bias_head + pos] (in elements; bias_head = 0: one bias for every head) is added to
 // the score of the stored position pos after the scale.  bias = NULL is spamd_attention
 extern "C" int spamd_attention_bias(int val_dtype, int idx_dtype, int64_t M, int64_t N, int64_t nnz, int64_t H, int64_t D, int64_t Dv,
@@ -458,27 +537,9 @@ extern "C" int spamd_attention_bias(int val_dtype, int idx_dtype, int64_t M, int
                                     int64_t v_head, int has_scale, double scale, int group, int64_t short_max, int64_t chunk,
                                     int64_t max_len, const void* bias, int64_t bias_head, void* ws, int64_t ws_bytes, void* out,
                                     void* stream) {
-  if (val_dtype != SPAMD_F32 && val_dtype != SPAMD_F64) return SPAMD_ETYPE;
-  if (idx_dtype != SPAMD_I32 && idx_dtype != SPAMD_I64) return SPAMD_ETYPE;
-  if (M < 0 || N < 0 || nnz < 0 || H < 0 || D < 0 || Dv < 0 || max_len < 0 || max_len > nnz) return SPAMD_EINVAL;
-  if (D > INT32_MAX - 128 || Dv > INT32_MAX - 128) return SPAMD_EINVAL;   // (row widths are 32-bit in the kernels)
-  if (q_pitch < 0 || q_head < 0 || k_pitch < 0 || k_head < 0 || v_pitch < 0 || v_head < 0) return SPAMD_EINVAL;
-  if (bias_head < 0) return SPAMD_EINVAL;
-  if (group != 8 && group != 16 && group != 32 && group != 64) return SPAMD_EINVAL;
-  if (chunk < 64 || chunk > ATTENTION_MAX_CHUNK || chunk % 64 || short_max < 0 || short_max > 64) return SPAMD_EINVAL;
-  if (M == 0 || H == 0 || Dv == 0) return 0;
-  if (!out || !s_ptr) return SPAMD_EINVAL;
-  if (nnz > 0 && (!s_idx || !s_val || !k || !v || (D > 0 && !q))) return SPAMD_EINVAL;
-  if (max_len > chunk && (!ws || ws_bytes < spamd_attention_ws_bytes(val_dtype, nnz, H, Dv, chunk))) return SPAMD_EWS;
-  hipStream_t st = (hipStream_t)stream;
-  SPAMD_DISPATCH_IDX(idx_dtype, I, {
-    if (val_dtype == SPAMD_F32)
-      return attention_in<float, I>(M, nnz, H, D, Dv, s_ptr, s_idx, s_val, q, q_pitch, q_head, k, k_pitch, k_head, v, v_pitch,
-                                    v_head, has_scale, scale, group, short_max, chunk, max_len, bias, bias_head, ws, out, st);
-    return attention_in<double, I>(M, nnz, H, D, Dv, s_ptr, s_idx, s_val, q, q_pitch, q_head, k, k_pitch, k_head, v, v_pitch,
-                                   v_head, has_scale, scale, group, short_max, chunk, max_len, bias, bias_head, ws, out, st);
-  })
-  return SPAMD_ETYPE;
+  return spamd_attention_dropout(val_dtype, idx_dtype, M, N, nnz, H, D, Dv, s_ptr, s_idx, s_val, q, q_pitch, q_head, k, k_pitch, k_head,
+                                 v, v_pitch, v_head, has_scale, scale, group, short_max, chunk, max_len, bias, bias_head, 0.0, 0, 0, ws,
+                                 ws_bytes, out, stream);
 }
 
 extern "C" int spamd_attention(int val_dtype, int idx_dtype, int64_t M, int64_t N, int64_t nnz, int64_t H, int64_t D, int64_t Dv,
@@ -489,4 +550,17 @@ extern "C" int spamd_attention(int val_dtype, int idx_dtype, int64_t M, int64_t 
   return spamd_attention_bias(val_dtype, idx_dtype, M, N, nnz, H, D, Dv, s_ptr, s_idx, s_val, q, q_pitch, q_head, k, k_pitch, k_head,
                               v, v_pitch, v_head, has_scale, scale, group, short_max, chunk, max_len, nullptr, 0, ws, ws_bytes, out,
                               stream);
+}
+
+// the keep decisions by themselves, from the device helper the attention kernels call: out[h * nnz + p] = 1 when the stored
+// position pos0 + p of head head0 + h is kept at `rate` under `seed`, else 0 (h < H, p < nnz)
+extern "C" int spamd_attention_keep(int64_t nnz, int64_t H, int64_t pos0, int64_t head0, double rate, int64_t seed, uint8_t* out,
+                                    void* stream) {
+  if (nnz < 0 || H < 0 || pos0 < 0 || head0 < 0 || !dropout_rate_ok(rate)) return SPAMD_EINVAL;
+  if (nnz == 0 || H == 0) return 0;
+  if (H > INT64_MAX / nnz || !out) return SPAMD_EINVAL;
+  const int64_t total = nnz * H;
+  hipLaunchKernelGGL(at_keep_kernel, dim3(at_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, nnz, total, (uint64_t)pos0,
+                     (uint64_t)head0, (uint64_t)seed, dropout_threshold(rate), out);
+  return launch_status();
 }

@@ -13,6 +13,8 @@
 //          folded by halving, the piece sums added in piece order
 //   z_i  = p_i * (e_i - delta);  y_i = s_i * z_i;  y_i = scale * y_i when a scale is given
 //   dbias[pos_i] = z_i with a bias (spamd_attention_grad_bias): t_i then carries A15's bias step, and the row pass stores z_i once
+//   with dropout (spamd_attention_grad_dropout): keep_i is recomputed; ed_i = keep_i ? e_i * c : +0.0 takes the place of e_i in
+//          u_i, delta and z_i, and pd_i = keep_i ? p_i * c : +0.0 is what the row pass parks for dv - the column pass is unchanged
 //   dq[r, j]: pieces of `chunk`; a piece starts at +0.0 and takes acc = fma(y_i, k[c_i, j], acc), i ascending; piece sums in
 //          piece order
 // Column c of one head, the stored elements of column c in stored order (positions pos_i = cperm[..], rows r_i = crow[..]), cut
@@ -27,6 +29,7 @@
 // Column forms, by the column's length m: a sub-group of CG lanes per (column, head) up to short_max, a wave up to chunk, both
 // with lanes along Dv and then D; longer columns in pieces of `chunk` (a wave per piece) and a join in piece order.
 #include "attention_common.h"
+#include "attention_dropout.h"
 #include "exp_det.h"
 
 namespace spamd {
@@ -103,10 +106,13 @@ __device__ __forceinline__ void ag_gather_acc(const T* __restrict__ vals, const 
 }
 
 // ---- row pass, short: a sub-group of G lanes per (row, head) ---------------------------------------------------------------------
-template <typename T, typename I, int G, bool B>
+// (P: with dropout - spamd_attention_grad_dropout; P = false compiles as before it existed, AtDrop<T, false> being an empty argument)
+template <typename T, typename I, int G, bool B, bool P>
 __global__ void __launch_bounds__(256)
-ag_short_kernel(AgIn<T, I> in, int64_t short_max, AtBias<T, B> bz) {
+ag_short_kernel(AgIn<T, I> in, int64_t short_max, AtMods<T, B, P> mz) {
 #pragma clang fp contract(off)
+  const AtBias<T, B>& bz = mz;
+  const AtDrop<T, P>& dz = mz;
   constexpr int V = 64 / G;
   constexpr int GPB = 256 / G;
   const int sub = threadIdx.x % G;
@@ -185,6 +191,15 @@ ag_short_kernel(AgIn<T, I> in, int64_t short_max, AtBias<T, B> bz) {
 #pragma unroll
     for (int r = 0; r < V; ++r) t[r] = t[r] / s;
     // phase 3: delta = sum p e (accumulator l holds u[l]: one piece of at most 64), then y; p and y go to the workspace
+    [[maybe_unused]] T pd[P ? V : 1];   // with dropout: pd_i = keep_i ? p_i * c : +0.0 is parked, and e becomes ed_i likewise
+    if constexpr (P) {
+#pragma unroll
+      for (int r = 0; r < V; ++r) {
+        const bool kept = sub + r * G < n && dz.keep(head, b + sub + r * G);
+        pd[r] = dz.mul(kept, t[r]);
+        ev[r] = dz.mul(kept, ev[r]);
+      }
+    }
 #pragma unroll
     for (int r = 0; r < V; ++r) a[r] = sub + r * G < n ? t[r] * ev[r] : T(0);
 #pragma unroll
@@ -198,7 +213,8 @@ ag_short_kernel(AgIn<T, I> in, int64_t short_max, AtBias<T, B> bz) {
       const T z = in.zval(t[r], ev[r], delta);
       ev[r] = in.yof(sv[r], z);   // ev holds y from here on
       if (i < n) {
-        wp[b + i] = t[r];
+        if constexpr (P) wp[b + i] = pd[r];
+        else wp[b + i] = t[r];
         wy[b + i] = ev[r];
         if constexpr (B)
           if (bz.db) bz.db[head * in.nnz + b + i] = z;
@@ -236,10 +252,12 @@ ag_short_kernel(AgIn<T, I> in, int64_t short_max, AtBias<T, B> bz) {
 }
 
 // ---- row pass, wide: a wave (one workgroup) per (row, head), t / p and e / y in LDS -------------------------------------------------
-template <typename T, typename I, bool B>
+template <typename T, typename I, bool B, bool P>
 __global__ void __launch_bounds__(64)
-ag_wide_kernel(AgIn<T, I> in, int64_t above, int64_t upto, AtBias<T, B> bz) {
+ag_wide_kernel(AgIn<T, I> in, int64_t above, int64_t upto, AtMods<T, B, P> mz) {
 #pragma clang fp contract(off)
+  const AtBias<T, B>& bz = mz;
+  const AtDrop<T, P>& dz = mz;
   extern __shared__ __attribute__((aligned(16))) unsigned char ag_smem[];
   T* __restrict__ lt = reinterpret_cast<T*>(ag_smem);   // `upto` values: t, then p
   T* __restrict__ le = lt + upto;                       // `upto` values: e, then y
@@ -307,6 +325,11 @@ ag_wide_kernel(AgIn<T, I> in, int64_t above, int64_t upto, AtBias<T, B> bz) {
       for (int x = lane; x < n; x += 64) {
         const T p = lt[x] / s;
         lt[x] = p;
+        if constexpr (P) {   // ed_i takes the place of e_i; pd_i is parked here, where the decision is at hand
+          const bool kept = dz.keep(head, b + x);
+          le[x] = dz.mul(kept, le[x]);
+          wp[b + x] = dz.mul(kept, p);
+        }
         const T u = p * le[x];
         acc = x == lane ? u : acc + u;
       }
@@ -315,7 +338,7 @@ ag_wide_kernel(AgIn<T, I> in, int64_t above, int64_t upto, AtBias<T, B> bz) {
         const T z = in.zval(lt[x], le[x], delta);
         const T y = in.yof(in.sv[b + x], z);
         le[x] = y;
-        wp[b + x] = lt[x];
+        if constexpr (!P) wp[b + x] = lt[x];
         wy[b + x] = y;
         if constexpr (B)
           if (bz.db) bz.db[head * in.nnz + b + x] = z;
@@ -342,8 +365,8 @@ __host__ __device__ __forceinline__ int64_t ag_ws_values(int64_t nnz, int64_t nw
 }
 
 // row phases: 0 t, e and piece maxima; 1 piece sums of exp; 2 p and piece deltas; 3 y; 4 dq pieces.  Column phase: 5 dv | dk pieces
-template <typename T, typename I, int PHASE, bool B>
-__device__ __forceinline__ void ag_piece(const AgIn<T, I>& in, const AtBias<T, B>& bz, int64_t head, int64_t row, int64_t b, int64_t s, int64_t e,
+template <typename T, typename I, int PHASE, bool B, bool P>
+__device__ __forceinline__ void ag_piece(const AgIn<T, I>& in, const AtBias<T, B>& bz, const AtDrop<T, P>& dz, int64_t head, int64_t row, int64_t b, int64_t s, int64_t e,
                                          int64_t chunk, int64_t nwin, int lane, T* __restrict__ ws) {
 #pragma clang fp contract(off)
   T* __restrict__ wp = ws;
@@ -395,6 +418,7 @@ __device__ __forceinline__ void ag_piece(const AgIn<T, I>& in, const AtBias<T, B
     for (int64_t x = s + lane; x < e; x += 64) {
       const T p = exp_det(wp[x] - m) / sum;
       wp[x] = p;
+      if constexpr (P) wy[x] = dz.mul(dz.keep(head, x), wy[x]);   // ed_i takes the place of e_i
       const T u = p * wy[x];
       acc = x == s + lane ? u : acc + u;
     }
@@ -406,6 +430,7 @@ __device__ __forceinline__ void ag_piece(const AgIn<T, I>& in, const AtBias<T, B
       const T s_x = in.sv[x];
       const T z = in.zval(wp[x], wy[x], delta);
       wy[x] = in.yof(s_x, z);
+      if constexpr (P) wp[x] = dz.mul(dz.keep(head, x), wp[x]);   // pd_i is parked for the column pass (the decision again)
       if constexpr (B)
         if (bz.db) bz.db[head * in.nnz + x] = z;
     }
@@ -433,9 +458,12 @@ __device__ __forceinline__ void ag_piece(const AgIn<T, I>& in, const AtBias<T, B
 }
 
 // a wave per window of `chunk` positions: the window holds at most two piece starts of long rows (csrc/attention.hip)
-template <typename T, typename I, int PHASE, bool B>
+// (P: the phases that see dropout are 2 - ed_i - and 3 - pd_i)
+template <typename T, typename I, int PHASE, bool B, bool P>
 __global__ void __launch_bounds__(256)
-ag_piece_kernel(AgIn<T, I> in, int64_t chunk, int64_t nwin, AtBias<T, B> bz) {
+ag_piece_kernel(AgIn<T, I> in, int64_t chunk, int64_t nwin, AtMods<T, B, P> mz) {
+  const AtBias<T, B>& bz = mz;
+  const AtDrop<T, P>& dz = mz;
   const int lane = threadIdx.x & 63;
   const I* __restrict__ ptr = PHASE == 5 ? in.cptr : in.ptr;
   const int64_t R = PHASE == 5 ? in.N : in.M, nnz = in.nnz;
@@ -449,13 +477,13 @@ ag_piece_kernel(AgIn<T, I> in, int64_t chunk, int64_t nwin, AtBias<T, B> bz) {
       const int64_t b0 = (int64_t)ptr[r0], e0 = (int64_t)ptr[r0 + 1];
       if (e0 - b0 > chunk) {
         const int64_t s = b0 + (lo - b0 + chunk - 1) / chunk * chunk;   // the one piece start of this row in [lo, lo + chunk)
-        if (s < hi && s < e0) ag_piece<T, I, PHASE, B>(in, bz, head, r0, b0, s, s + chunk < e0 ? s + chunk : e0, chunk, nwin, lane, ws);
+        if (s < hi && s < e0) ag_piece<T, I, PHASE, B, P>(in, bz, dz, head, r0, b0, s, s + chunk < e0 ? s + chunk : e0, chunk, nwin, lane, ws);
       }
     }
     const int64_t r1 = at_row_of(ptr, R, hi - 1);
     if (r1 > r0) {   // starts inside the window; only the last such row can be longer than the window
       const int64_t b1 = (int64_t)ptr[r1], e1 = (int64_t)ptr[r1 + 1];
-      if (e1 - b1 > chunk) ag_piece<T, I, PHASE, B>(in, bz, head, r1, b1, b1, b1 + chunk, chunk, nwin, lane, ws);
+      if (e1 - b1 > chunk) ag_piece<T, I, PHASE, B, P>(in, bz, dz, head, r1, b1, b1, b1 + chunk, chunk, nwin, lane, ws);
     }
   }
 }
@@ -581,32 +609,33 @@ static unsigned ag_grid(int64_t items, int64_t per_block) {
     if (int rc = launch_status()) return rc;                              \
   } while (0)
 
-template <typename T, typename I, bool B>
-static int attention_grad_typed(AgIn<T, I> in, AtBias<T, B> bz, int group, int col_group, int64_t short_max, int64_t chunk, int64_t max_row,
+template <typename T, typename I, bool B, bool P>
+static int attention_grad_typed(AgIn<T, I> in, AtBias<T, B> bz, AtDrop<T, P> dz, int group, int col_group, int64_t short_max, int64_t chunk, int64_t max_row,
                                 int64_t max_col, hipStream_t st) {
   const unsigned gy = (unsigned)in.H;
   const int64_t nwin = ceil_div(in.nnz, chunk);
   const dim3 pg(ag_grid(nwin, 4), gy);
   const AtBias<T, false> nob{};   // the launches that neither form a score nor hold z
+  const AtDrop<T, false> nod{};   // the launches that neither form ed nor park pd
   if (in.M > 0) {   // the row pass; the short form always runs: it writes the dq rows of the rows without a stored element
     const dim3 sg(ag_grid(in.M, 256 / group), gy);
-    if (group == 8) AG_LAUNCH((ag_short_kernel<T, I, 8, B>), sg, dim3(256), 0, in, short_max, bz);
-    else if (group == 16) AG_LAUNCH((ag_short_kernel<T, I, 16, B>), sg, dim3(256), 0, in, short_max, bz);
-    else if (group == 32) AG_LAUNCH((ag_short_kernel<T, I, 32, B>), sg, dim3(256), 0, in, short_max, bz);
-    else AG_LAUNCH((ag_short_kernel<T, I, 64, B>), sg, dim3(256), 0, in, short_max, bz);
+    if (group == 8) AG_LAUNCH((ag_short_kernel<T, I, 8, B, P>), sg, dim3(256), 0, in, short_max, AtMods<T, B, P>(bz, dz));
+    else if (group == 16) AG_LAUNCH((ag_short_kernel<T, I, 16, B, P>), sg, dim3(256), 0, in, short_max, AtMods<T, B, P>(bz, dz));
+    else if (group == 32) AG_LAUNCH((ag_short_kernel<T, I, 32, B, P>), sg, dim3(256), 0, in, short_max, AtMods<T, B, P>(bz, dz));
+    else AG_LAUNCH((ag_short_kernel<T, I, 64, B, P>), sg, dim3(256), 0, in, short_max, AtMods<T, B, P>(bz, dz));
     if (std::min(max_row, chunk) > short_max)
-      AG_LAUNCH((ag_wide_kernel<T, I, B>), dim3(ag_grid(in.M, 64), gy), dim3(64), (size_t)(2 * chunk) * sizeof(T), in, short_max, chunk,
-                bz);
+      AG_LAUNCH((ag_wide_kernel<T, I, B, P>), dim3(ag_grid(in.M, 64), gy), dim3(64), (size_t)(2 * chunk) * sizeof(T), in, short_max, chunk,
+                AtMods<T, B, P>(bz, dz));
     if (max_row > chunk) {
       const dim3 jg(ag_grid(in.M, 256), gy);
-      AG_LAUNCH((ag_piece_kernel<T, I, 0, B>), pg, dim3(256), 0, in, chunk, nwin, bz);
+      AG_LAUNCH((ag_piece_kernel<T, I, 0, B, false>), pg, dim3(256), 0, in, chunk, nwin, AtMods<T, B, false>(bz, nod));
       AG_LAUNCH((ag_join_kernel<T, I, 0>), jg, dim3(256), 0, in, chunk, nwin);
-      AG_LAUNCH((ag_piece_kernel<T, I, 1, false>), pg, dim3(256), 0, in, chunk, nwin, nob);
+      AG_LAUNCH((ag_piece_kernel<T, I, 1, false, false>), pg, dim3(256), 0, in, chunk, nwin, AtMods<T, false, false>(nob, nod));
       AG_LAUNCH((ag_join_kernel<T, I, 1>), jg, dim3(256), 0, in, chunk, nwin);
-      AG_LAUNCH((ag_piece_kernel<T, I, 2, false>), pg, dim3(256), 0, in, chunk, nwin, nob);
+      AG_LAUNCH((ag_piece_kernel<T, I, 2, false, P>), pg, dim3(256), 0, in, chunk, nwin, AtMods<T, false, P>(nob, dz));
       AG_LAUNCH((ag_join_kernel<T, I, 2>), jg, dim3(256), 0, in, chunk, nwin);
-      AG_LAUNCH((ag_piece_kernel<T, I, 3, B>), pg, dim3(256), 0, in, chunk, nwin, bz);
-      AG_LAUNCH((ag_piece_kernel<T, I, 4, false>), pg, dim3(256), 0, in, chunk, nwin, nob);
+      AG_LAUNCH((ag_piece_kernel<T, I, 3, B, P>), pg, dim3(256), 0, in, chunk, nwin, AtMods<T, B, P>(bz, dz));
+      AG_LAUNCH((ag_piece_kernel<T, I, 4, false, false>), pg, dim3(256), 0, in, chunk, nwin, AtMods<T, false, false>(nob, nod));
       AG_LAUNCH((ag_join_kernel<T, I, 3>), jg, dim3(256), 0, in, chunk, nwin);
     }
   }
@@ -619,7 +648,7 @@ static int attention_grad_typed(AgIn<T, I> in, AtBias<T, B> bz, int group, int c
     if (std::min(max_col, chunk) > short_max)
       AG_LAUNCH((ag_col_kernel<T, I, 64>), dim3(ag_grid(in.N, 4), gy), dim3(256), 0, in, short_max, chunk);
     if (max_col > chunk) {
-      AG_LAUNCH((ag_piece_kernel<T, I, 5, false>), pg, dim3(256), 0, in, chunk, nwin, nob);
+      AG_LAUNCH((ag_piece_kernel<T, I, 5, false, false>), pg, dim3(256), 0, in, chunk, nwin, AtMods<T, false, false>(nob, nod));
       AG_LAUNCH((ag_join_kernel<T, I, 4>), dim3(ag_grid(in.N, 256), gy), dim3(256), 0, in, chunk, nwin);
     }
   }
@@ -639,6 +668,9 @@ struct AgArgs {
   const void* bias;
   int64_t bias_head;
   void* dbias;
+  double rate;   // 0: no dropout - the kernels of spamd_attention_grad / spamd_attention_grad_bias
+  uint64_t seed;
+  int64_t head0;
 };
 
 template <typename T, typename I>
@@ -651,14 +683,19 @@ static int attention_grad_in(const AgArgs& a, hipStream_t st) {
                   std::min<int64_t>(a.H - h0, 65535), a.nnz, (int)a.D, (int)a.Dv, (T)a.scale, a.has_scale != 0,
                   a.ws ? (T*)a.ws + h0 * ws_head : nullptr, ws_head, (T*)a.dq + h0 * a.M * a.D, (T*)a.dk + h0 * a.N * a.D,
                   (T*)a.dv + h0 * a.N * a.Dv};
+    const AtBias<T, true> bz{(const T*)a.bias + h0 * a.bias_head, a.bias_head, a.dbias ? (T*)a.dbias + h0 * a.nnz : nullptr};
+    const AtBias<T, false> nob{};
+    // (the head's number goes on across the launches: head 65535 does not repeat head 0's decisions)
+    const AtDrop<T, true> dz{a.seed, (uint64_t)a.head0 + (uint64_t)h0, dropout_threshold(a.rate), (T)(1.0 / (1.0 - a.rate))};
+    const AtDrop<T, false> nod{};
     int rc;
-    if (a.bias)
-      rc = attention_grad_typed<T, I, true>(in, AtBias<T, true>{(const T*)a.bias + h0 * a.bias_head, a.bias_head,
-                                                                 a.dbias ? (T*)a.dbias + h0 * a.nnz : nullptr},
-                                            a.group, a.col_group, a.short_max, a.chunk, a.max_row, a.max_col, st);
-    else
-      rc = attention_grad_typed<T, I, false>(in, AtBias<T, false>{}, a.group, a.col_group, a.short_max, a.chunk, a.max_row, a.max_col,
-                                             st);
+    if (a.rate > 0.0) {
+      if (a.bias) rc = attention_grad_typed<T, I, true, true>(in, bz, dz, a.group, a.col_group, a.short_max, a.chunk, a.max_row, a.max_col, st);
+      else rc = attention_grad_typed<T, I, false, true>(in, nob, dz, a.group, a.col_group, a.short_max, a.chunk, a.max_row, a.max_col, st);
+    } else {
+      if (a.bias) rc = attention_grad_typed<T, I, true, false>(in, bz, nod, a.group, a.col_group, a.short_max, a.chunk, a.max_row, a.max_col, st);
+      else rc = attention_grad_typed<T, I, false, false>(in, nob, nod, a.group, a.col_group, a.short_max, a.chunk, a.max_row, a.max_col, st);
+    }
     if (rc) return rc;
   }
   return 0;
@@ -675,16 +712,18 @@ extern "C" int64_t spamd_attention_grad_ws_bytes(int val_dtype, int64_t nnz, int
   return H * ag_ws_values(nnz, nnz > chunk ? ceil_div(nnz, chunk) : 0, D, Dv) * esz;
 }
 
-// the entry with an additive bias (spamd_attention_bias): t_i and p_i are recomputed with it, and dbias (H, nnz) contiguous, when
-// not NULL, takes z_i at [head][stored position].  bias = NULL is spamd_attention_grad (dbias is not written)
-extern "C" int spamd_attention_grad_bias(int val_dtype, int idx_dtype, int64_t M, int64_t N, int64_t nnz, int64_t H, int64_t D,
+// the entry with dropout (spamd_attention_dropout): keep_i is recomputed from (seed, head0 + head, stored position); ed_i =
+// keep_i ? e_i * c : +0.0 takes the place of e_i in u_i, delta and z_i, and the row pass parks pd_i = keep_i ? p_i * c : +0.0
+// in the place of p_i, so the column pass is the one without dropout.  rate = 0 is spamd_attention_grad_bias (the same
+// kernels); bias = NULL is no bias (dbias is not written)
+extern "C" int spamd_attention_grad_dropout(int val_dtype, int idx_dtype, int64_t M, int64_t N, int64_t nnz, int64_t H, int64_t D,
                                     int64_t Dv, const void* s_ptr, const void* s_idx, const void* s_val, const void* c_ptr,
                                     const int64_t* c_perm, const void* c_row, const void* q, int64_t q_pitch, int64_t q_head,
                                     const void* k, int64_t k_pitch, int64_t k_head, const void* v, int64_t v_pitch,
                                     int64_t v_head, const void* g, int64_t g_pitch, int64_t g_head, int has_scale, double scale,
                                     int group, int col_group, int64_t short_max, int64_t chunk, int64_t max_row, int64_t max_col,
-                                    const void* bias, int64_t bias_head, void* dbias, void* ws, int64_t ws_bytes, void* dq, void* dk,
-                                    void* dv, void* stream) {
+                                    const void* bias, int64_t bias_head, void* dbias, double rate, int64_t seed, int64_t head0,
+                                    void* ws, int64_t ws_bytes, void* dq, void* dk, void* dv, void* stream) {
   if (val_dtype != SPAMD_F32 && val_dtype != SPAMD_F64) return SPAMD_ETYPE;
   if (idx_dtype != SPAMD_I32 && idx_dtype != SPAMD_I64) return SPAMD_ETYPE;
   if (M < 0 || N < 0 || nnz < 0 || H < 0 || D < 0 || Dv < 0) return SPAMD_EINVAL;
@@ -693,6 +732,7 @@ extern "C" int spamd_attention_grad_bias(int val_dtype, int idx_dtype, int64_t M
   if (q_pitch < 0 || q_head < 0 || k_pitch < 0 || k_head < 0 || v_pitch < 0 || v_head < 0 || g_pitch < 0 || g_head < 0)
     return SPAMD_EINVAL;
   if (bias_head < 0) return SPAMD_EINVAL;
+  if (!dropout_rate_ok(rate) || head0 < 0) return SPAMD_EINVAL;
   if (group != 8 && group != 16 && group != 32 && group != 64) return SPAMD_EINVAL;
   if (col_group != 8 && col_group != 16 && col_group != 32 && col_group != 64) return SPAMD_EINVAL;
   if (chunk < 64 || chunk > ATTENTION_MAX_CHUNK || chunk % 64 || short_max < 0 || short_max > 64) return SPAMD_EINVAL;
@@ -707,13 +747,29 @@ extern "C" int spamd_attention_grad_bias(int val_dtype, int idx_dtype, int64_t M
   }
   const AgArgs a{M, N, nnz, H, D, Dv, s_ptr, s_idx, s_val, c_ptr, c_perm, c_row, q, k, v, g, q_pitch, q_head, k_pitch, k_head,
                  v_pitch, v_head, g_pitch, g_head, has_scale, scale, group, col_group, short_max, chunk, max_row, max_col, ws, dq,
-                 dk, dv, bias, bias_head, dbias};
+                 dk, dv, bias, bias_head, dbias, rate, (uint64_t)seed, head0};
   hipStream_t st = (hipStream_t)stream;
   SPAMD_DISPATCH_IDX(idx_dtype, I, {
     if (val_dtype == SPAMD_F32) return attention_grad_in<float, I>(a, st);
     return attention_grad_in<double, I>(a, st);
   })
   return SPAMD_ETYPE;
+}
+
+// the entry with an additive bias (spamd_attention_bias): t_i and p_i are recomputed with it, and dbias (H, nnz) contiguous, when
+// not NULL, takes z_i at [head][stored position].  bias = NULL is spamd_attention_grad (dbias is not written)
+extern "C" int spamd_attention_grad_bias(int val_dtype, int idx_dtype, int64_t M, int64_t N, int64_t nnz, int64_t H, int64_t D,
+                                    int64_t Dv, const void* s_ptr, const void* s_idx, const void* s_val, const void* c_ptr,
+                                    const int64_t* c_perm, const void* c_row, const void* q, int64_t q_pitch, int64_t q_head,
+                                    const void* k, int64_t k_pitch, int64_t k_head, const void* v, int64_t v_pitch,
+                                    int64_t v_head, const void* g, int64_t g_pitch, int64_t g_head, int has_scale, double scale,
+                                    int group, int col_group, int64_t short_max, int64_t chunk, int64_t max_row, int64_t max_col,
+                                    const void* bias, int64_t bias_head, void* dbias, void* ws, int64_t ws_bytes, void* dq, void* dk,
+                                    void* dv, void* stream) {
+  return spamd_attention_grad_dropout(val_dtype, idx_dtype, M, N, nnz, H, D, Dv, s_ptr, s_idx, s_val, c_ptr, c_perm, c_row, q, q_pitch,
+                                      q_head, k, k_pitch, k_head, v, v_pitch, v_head, g, g_pitch, g_head, has_scale, scale, group,
+                                      col_group, short_max, chunk, max_row, max_col, bias, bias_head, dbias, 0.0, 0, 0, ws, ws_bytes, dq,
+                                      dk, dv, stream);
 }
 
 extern "C" int spamd_attention_grad(int val_dtype, int idx_dtype, int64_t M, int64_t N, int64_t nnz, int64_t H, int64_t D,

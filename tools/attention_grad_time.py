@@ -6,10 +6,13 @@ a user had to write before - in the same process, on the same inputs, a Python l
     dq = Y @ k;  dk = Y.T @ q;  dv = P.T @ g
 
     python tools/attention_grad_time.py [--reps 20] [--rounds 5] [--sweep] [--sizes graph heads hub hubcol small]
-                                        [--bias none|shared|head]
+                                        [--bias none|shared|head] [--dropout RATE]
 
   --bias shared | head: with an additive bias b (a sparse array of the mask's pattern in the composed expression, where
   P = softmax(sddmm(s, q, bt=k) * c + b) and dbias = Z is one more result), beside the fused call without a bias.
+  --dropout RATE (combines with --bias): with attention dropout; the composed expression takes keep_scaled of
+  tools/attention_time.py, built outside the timed region - E = sddmm(pattern, g, bt=v) * keep_scaled, dv = (P * keep_scaled).T @ g -
+  beside the fused call without dropout.
 
   sizes (a) graph, (b) heads, (c) hub and (d) small are those of tools/attention_time.py; hubcol is the transpose of (c): ONE hub
   COLUMN of 10^6 stored elements among 2^16 columns of 8.  The hub cases are reported only.
@@ -32,7 +35,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import sparse_amd  # noqa: E402
-from attention_time import build as build_forward, make_bias, rounds_of, wall_ms  # noqa: E402
+from attention_time import DROPOUT_SEED, build as build_forward, make_bias, make_keep, rounds_of, wall_ms  # noqa: E402
 from sparse_amd import _attention, _kernels as K  # noqa: E402
 
 
@@ -47,25 +50,29 @@ def build(tag, d):
     return s, pattern, q, k, v, g, scale
 
 
-def composed_head(s, pattern, q, k, v, g, scale, b=None):
+def composed_head(s, pattern, q, k, v, g, scale, b=None, ks=None):
     if b is None:
         P = sparse_amd.softmax(sparse_amd.sddmm(s, q, bt=k), -1, scale=scale)
     else:
         P = sparse_amd.softmax(sparse_amd.sddmm(s, q, bt=k) * scale + b, -1)
     E = sparse_amd.sddmm(pattern, g, bt=v)
+    Pd = P
+    if ks is not None:
+        E, Pd = E * ks, P * ks
     U = P * E
     delta = U.sum(axis=1)
     delta = delta.todense() if hasattr(delta, "todense") else delta
     Z = U - P * delta[:, None]
     Y = (s * Z) * scale
-    return (sparse_amd.matmul(Y, k), sparse_amd.matmul(Y.T, q), sparse_amd.matmul(P.T, g)) + (() if b is None else (Z,))
+    return (sparse_amd.matmul(Y, k), sparse_amd.matmul(Y.T, q), sparse_amd.matmul(Pd.T, g)) + (() if b is None else (Z,))
 
 
-def composed(s, pattern, q, k, v, g, scale, sp=None):
+def composed(s, pattern, q, k, v, g, scale, sp=None, ks=None):
     """(dq, dk, dv), and with a bias the elementwise dbias (a sparse array per head) as a fourth result"""
     if q.ndim == 2:
-        return composed_head(s, pattern, q, k, v, g, scale, None if sp is None else sp[0])
-    outs = [composed_head(s, pattern, q[h], k[h], v[h], g[h], scale, None if sp is None else sp[h]) for h in range(q.shape[0])]
+        return composed_head(s, pattern, q, k, v, g, scale, None if sp is None else sp[0], None if ks is None else ks[0])
+    outs = [composed_head(s, pattern, q[h], k[h], v[h], g[h], scale, None if sp is None else sp[h], None if ks is None else ks[h])
+            for h in range(q.shape[0])]
     return tuple(torch.stack([torch.as_tensor(o[i]) for o in outs]) for i in range(3)) + (() if sp is None else ([o[3] for o in outs],))
 
 
@@ -79,26 +86,32 @@ def traffic(s, H, D, Dv, esz, isz):
 
 
 def bias_case(args, base, s, pattern, q, k, v, g, scale):
+    """the calls with a bias, with dropout, or with both"""
     b, sp = make_bias(args.bias, s, q)
-    fused_call = lambda: sparse_amd.sparse_attention_grad(s, q, k, v, g, scale=scale, bias=b)                 # noqa: E731
+    ks = make_keep(args.dropout, s, q)
+    drop = dict(dropout=args.dropout, seed=DROPOUT_SEED) if args.dropout else {}
+    fused_call = lambda: sparse_amd.sparse_attention_grad(s, q, k, v, g, scale=scale, bias=b, **drop)         # noqa: E731
     first = wall_ms(fused_call)
     plan, max_row = s._attention_grad_plan, s._attention_plan["max_len"]
     reps = max(args.reps // 4, 2) if base["size"] in ("hub", "hubcol") else args.reps
     fused = rounds_of(fused_call, reps, args.rounds)
     plain = rounds_of(lambda: sparse_amd.sparse_attention_grad(s, q, k, v, g, scale=scale), reps, args.rounds)
+    nodrop = rounds_of(lambda: sparse_amd.sparse_attention_grad(s, q, k, v, g, scale=scale, bias=b), reps, args.rounds) if drop else fused
     data, indices, indptr = _attention._csr_of_mask(s)
     kernel = rounds_of(lambda: K.attention_grad_rows(indptr, indices, data, plan["colptr"], plan["colperm"], plan["colrows"], q, k, v,
-                                                     g, max_row, plan["max_col"], scale=scale, bias=b, want_dbias=True),
+                                                     g, max_row, plan["max_col"], scale=scale, bias=b, want_dbias=b is not None, **drop),
                        reps, args.rounds)
-    first_c = wall_ms(lambda: composed(s, pattern, q, k, v, g, scale, sp))
-    comp = rounds_of(lambda: composed(s, pattern, q, k, v, g, scale, sp), reps, args.rounds)
-    got, ref = fused_call(), composed(s, pattern, q, k, v, g, scale, sp)
+    first_c = wall_ms(lambda: composed(s, pattern, q, k, v, g, scale, sp, ks))
+    comp = rounds_of(lambda: composed(s, pattern, q, k, v, g, scale, sp, ks), reps, args.rounds)
+    got, ref = fused_call(), composed(s, pattern, q, k, v, g, scale, sp, ks)
     dev = q.device
     diff = [float((a.double() - torch.as_tensor(np.asarray(r) if not isinstance(r, torch.Tensor) else r).to(dev).double()).abs().max())
             for a, r in zip(got[:3], ref[:3])]
-    print(json.dumps({**base, "what": "attention_grad_bias", "bias": args.bias, "max_row": max_row, "max_col": plan["max_col"],
+    print(json.dumps({**base, "what": "attention_grad_dropout" if drop else "attention_grad_bias", "bias": args.bias,
+                      "dropout": args.dropout, "max_row": max_row, "max_col": plan["max_col"],
                       "first_call_wall_ms": first, "fused": fused, "kernels_alone": kernel, "fused_without_bias": plain,
-                      "bias_over_none": round(fused["ms"] / plain["ms"], 3), "composed_first_wall_ms": first_c, "composed": comp,
+                      "fused_without_dropout": nodrop, "bias_over_none": round(nodrop["ms"] / plain["ms"], 3),
+                      "dropout_over_none": round(fused["ms"] / nodrop["ms"], 3), "composed_first_wall_ms": first_c, "composed": comp,
                       "composed_over_fused": round(comp["ms"] / fused["ms"], 2), "fused_not_slower": fused["ms"] <= comp["ms"],
                       "max_abs_diff_dq_dk_dv": diff}), flush=True)
 
@@ -110,6 +123,7 @@ def main():
     ap.add_argument("--sizes", nargs="*", default=["graph", "heads", "hub", "hubcol", "small"])
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--bias", choices=["none", "shared", "head"], default="none")
+    ap.add_argument("--dropout", type=float, default=0.0)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("attention_grad_time.py measures on the GPU: no HIP device visible")
@@ -121,7 +135,7 @@ def main():
         s, pattern, q, k, v, g, scale = build(tag, d)
         H = 1 if q.ndim == 2 else int(q.shape[0])
         base = {"size": tag, "shape": s.shape, "nnz": s.nnz, "heads": H, "D": int(q.shape[-1]), "Dv": int(v.shape[-1])}
-        if args.bias != "none":
+        if args.bias != "none" or args.dropout:
             bias_case(args, base, s, pattern, q, k, v, g, scale)
             continue
         fused_call = lambda: sparse_amd.sparse_attention_grad(s, q, k, v, g, scale=scale)                 # noqa: E731

@@ -5,12 +5,20 @@
 through this library, in the same process, on the same inputs (the yardstick: it is what a user wrote before):
 
     python tools/attention_time.py [--reps 20] [--rounds 5] [--sweep] [--sizes graph heads hub small] [--bias none|shared|head]
+                                   [--dropout RATE]
 
   --bias shared | head: the calls with an additive bias per stored element (one for all heads, or one per head), beside
 
     matmul(softmax(sddmm(s, q, bt=k) * c + b), v)         with b a sparse array of the mask's pattern
 
   and beside the fused call without a bias (`bias_over_none`, reported only).
+  --dropout RATE (combines with --bias): the calls with attention dropout, beside
+
+    matmul(softmax(sddmm(s, q, bt=k) [* c + b], ...) * keep_scaled, v)
+
+  with keep_scaled a sparse array of the mask's pattern that holds 1 / (1 - RATE) where `sparse_attention_keep_mask` keeps
+  and 0 elsewhere, built OUTSIDE the timed region (which favours the composed side), and beside the fused call without
+  dropout (`dropout_over_none`, reported only).
 
   size (a) graph  a CSR graph of 2^17 nodes, mean degree 32 (row lengths Poisson), D = Dv = 64, float32
   size (b) heads  the same graph, H = 8 heads of D = Dv = 16, against a Python loop of the expression over the heads
@@ -106,10 +114,29 @@ def make_bias(mode, s, q):
     return b, sp
 
 
-def three_calls(s, q, k, v, scale, sp=None):
-    if sp is not None:
-        one = lambda q, k, v, b: sparse_amd.matmul(sparse_amd.softmax(sparse_amd.sddmm(s, q, bt=k) * scale + b, -1), v)   # noqa: E731
-        return one(q, k, v, sp[0]) if q.ndim == 2 else torch.stack([one(q[h], k[h], v[h], sp[h]) for h in range(q.shape[0])])
+DROPOUT_SEED = 29
+
+
+def make_keep(rate, s, q):
+    """keep_scaled of every head: sparse arrays of the mask's pattern, 1 / (1 - rate) where the element is kept, else 0"""
+    if not rate:
+        return None
+    lead = tuple(q.shape[:-2])
+    keep = sparse_amd.sparse_attention_keep_mask(s, lead, dropout=rate, seed=DROPOUT_SEED).reshape(-1, s.nnz)
+    scaled = keep.to(q.dtype) * (1.0 / (1.0 - rate))
+    return [sparse_amd.GCXS((scaled[h].contiguous(), s.indices, s.indptr), shape=s.shape, compressed_axes=(0,)) for h in range(scaled.shape[0])]
+
+
+def three_calls(s, q, k, v, scale, sp=None, ks=None):
+    if sp is not None or ks is not None:
+        def one(q, k, v, h):
+            if sp is not None:
+                p = sparse_amd.softmax(sparse_amd.sddmm(s, q, bt=k) * scale + sp[h], -1)
+            else:
+                p = sparse_amd.softmax(sparse_amd.sddmm(s, q, bt=k), -1, scale=scale)
+            return sparse_amd.matmul(p if ks is None else p * ks[h], v)
+
+        return one(q, k, v, 0) if q.ndim == 2 else torch.stack([torch.as_tensor(one(q[h], k[h], v[h], h)) for h in range(q.shape[0])])
     if q.ndim == 2:
         return sparse_amd.matmul(sparse_amd.softmax(sparse_amd.sddmm(s, q, bt=k), -1, scale=scale), v)
     return torch.stack([sparse_amd.matmul(sparse_amd.softmax(sparse_amd.sddmm(s, q[h], bt=k[h]), -1, scale=scale), v[h])
@@ -117,21 +144,27 @@ def three_calls(s, q, k, v, scale, sp=None):
 
 
 def bias_case(args, base, s, q, k, v, scale):
+    """the calls with a bias, with dropout, or with both"""
     b, sp = make_bias(args.bias, s, q)
-    first = wall_ms(lambda: sparse_amd.sparse_attention(s, q, k, v, scale=scale, bias=b))
+    ks = make_keep(args.dropout, s, q)
+    drop = dict(dropout=args.dropout, seed=DROPOUT_SEED) if args.dropout else {}
+    first = wall_ms(lambda: sparse_amd.sparse_attention(s, q, k, v, scale=scale, bias=b, **drop))
     max_len = s._attention_plan["max_len"]
     reps = max(args.reps // 4, 2) if base["size"] == "hub" else args.reps
-    fused = rounds_of(lambda: sparse_amd.sparse_attention(s, q, k, v, scale=scale, bias=b), reps, args.rounds)
+    fused = rounds_of(lambda: sparse_amd.sparse_attention(s, q, k, v, scale=scale, bias=b, **drop), reps, args.rounds)
     plain = rounds_of(lambda: sparse_amd.sparse_attention(s, q, k, v, scale=scale), reps, args.rounds)
+    nodrop = rounds_of(lambda: sparse_amd.sparse_attention(s, q, k, v, scale=scale, bias=b), reps, args.rounds) if drop else fused
     data, indices, indptr = _attention._csr_of_mask(s)
-    kernel = rounds_of(lambda: K.attention_rows(indptr, indices, data, q, k, v, max_len, scale=scale, bias=b), reps, args.rounds)
-    first3 = wall_ms(lambda: three_calls(s, q, k, v, scale, sp))
-    three = rounds_of(lambda: three_calls(s, q, k, v, scale, sp), reps, args.rounds)
-    got, ref = sparse_amd.sparse_attention(s, q, k, v, scale=scale, bias=b), three_calls(s, q, k, v, scale, sp)
+    kernel = rounds_of(lambda: K.attention_rows(indptr, indices, data, q, k, v, max_len, scale=scale, bias=b, **drop), reps, args.rounds)
+    first3 = wall_ms(lambda: three_calls(s, q, k, v, scale, sp, ks))
+    three = rounds_of(lambda: three_calls(s, q, k, v, scale, sp, ks), reps, args.rounds)
+    got, ref = sparse_amd.sparse_attention(s, q, k, v, scale=scale, bias=b, **drop), three_calls(s, q, k, v, scale, sp, ks)
     ref = ref if isinstance(ref, torch.Tensor) else torch.from_numpy(np.asarray(ref)).to(q.device)
-    print(json.dumps({**base, "what": "attention_bias", "bias": args.bias, "max_len": max_len, "first_call_wall_ms": first,
-                      "fused": fused, "kernel_alone": kernel, "fused_without_bias": plain,
-                      "bias_over_none": round(fused["ms"] / plain["ms"], 3), "composed_first_wall_ms": first3, "composed": three,
+    print(json.dumps({**base, "what": "attention_dropout" if drop else "attention_bias", "bias": args.bias, "dropout": args.dropout,
+                      "max_len": max_len, "first_call_wall_ms": first,
+                      "fused": fused, "kernel_alone": kernel, "fused_without_bias": plain, "fused_without_dropout": nodrop,
+                      "bias_over_none": round(nodrop["ms"] / plain["ms"], 3), "dropout_over_none": round(fused["ms"] / nodrop["ms"], 3),
+                      "composed_first_wall_ms": first3, "composed": three,
                       "composed_over_fused": round(three["ms"] / fused["ms"], 2), "fused_not_slower": fused["ms"] <= three["ms"],
                       "max_abs_diff": float((got.double() - ref.double()).abs().max())}), flush=True)
 
@@ -143,6 +176,7 @@ def main():
     ap.add_argument("--sizes", nargs="*", default=["graph", "heads", "hub", "small"])
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--bias", choices=["none", "shared", "head"], default="none")
+    ap.add_argument("--dropout", type=float, default=0.0)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("attention_time.py measures on the GPU: no HIP device visible")
@@ -154,7 +188,7 @@ def main():
         s, q, k, v, scale = build(tag, d)
         base = {"size": tag, "shape": s.shape, "nnz": s.nnz, "heads": 1 if q.ndim == 2 else int(q.shape[0]), "D": int(q.shape[-1]),
                 "Dv": int(v.shape[-1])}
-        if args.bias != "none":
+        if args.bias != "none" or args.dropout:
             bias_case(args, base, s, q, k, v, scale)
             continue
         first = wall_ms(lambda: sparse_amd.sparse_attention(s, q, k, v, scale=scale))

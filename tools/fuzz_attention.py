@@ -7,7 +7,8 @@ lengths (hubs beyond the chunk among many short rows), a share of empty rows, D 
 float, integer or boolean mask values, a query spread of 1 or 8, now and then a scale, a stored zero, an infinity or a NaN among
 the mask values - and the mask as a COO, a COO built unsorted, a CSR or a CSC; the operands as NumPy arrays, device tensors or
 row-strided device views; in half of the cases an additive bias, shared or per head, in the order of the array the caller holds,
-with -inf entries in some.  Prints one line per case; exits 1 at the first difference."""
+with -inf entries in some; in half of the cases a dropout of 0.1 to 0.9 under a 64-bit seed (the restatement of
+tests/attention_dropout_cases.py then).  Prints one line per case; exits 1 at the first difference."""
 import argparse
 import os
 import sys
@@ -19,6 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import attention_bias_cases as bc  # noqa: E402
+import attention_dropout_cases as dc  # noqa: E402
 import attention_cases as ac  # noqa: E402
 import attention_grad_cases as gc  # noqa: E402
 import softmax_cases as sc  # noqa: E402
@@ -89,13 +91,21 @@ def main():
         given = None if bias is None else np.ascontiguousarray(bias[..., order])
         if given is not None and how != "numpy":
             given = torch.from_numpy(given).to("cuda:0")
-        out = sparse_amd.sparse_attention(s, *ops, scale=scale, bias=given)
+        drng = np.random.default_rng([a.seed, case, 2])                     # (a stream of its own again)
+        drop = {}
+        if drng.random() < 0.5:                                              # dropout in half of the cases
+            drop = dict(dropout=float(drng.choice([0.1, 0.5, 0.6, 0.9])), seed=int(drng.integers(0, 1 << 64, dtype=np.uint64)))
+        out = sparse_amd.sparse_attention(s, *ops, scale=scale, bias=given, **drop)
         out = out if isinstance(out, np.ndarray) else out.cpu().numpy()
-        want = ac.attention_heads(indptr, indices, vals, q, k, v, chunk, scale) if bias is None else \
-            bc.attention_bias_heads(indptr, indices, vals, q, k, v, chunk, scale, bias)
+        if drop:
+            want = dc.attention_dropout_heads(indptr, indices, vals, q, k, v, chunk, scale, bias, drop["dropout"], drop["seed"])
+        elif bias is None:
+            want = ac.attention_heads(indptr, indices, vals, q, k, v, chunk, scale)
+        else:
+            want = bc.attention_bias_heads(indptr, indices, vals, q, k, v, chunk, scale, bias)
         ok = sc.same_bits(out, want)
         print(f"case {case}: {np.dtype(dtype)} mask {np.dtype(mdt)} {np.dtype(idx)} {layout} {how} chunk {chunk} group {group} scale {scale} "
-              f"bias {None if bias is None else bias.shape} D {D} Dv {Dv} heads {lead} rows {len(lengths)} nnz {len(vals)} longest {max(lengths)}: {'same bits' if ok else 'DIFFERENT'}",
+              f"bias {None if bias is None else bias.shape} dropout {drop.get('dropout')} D {D} Dv {Dv} heads {lead} rows {len(lengths)} nnz {len(vals)} longest {max(lengths)}: {'same bits' if ok else 'DIFFERENT'}",
               flush=True)
         if not ok:
             raise SystemExit(1)

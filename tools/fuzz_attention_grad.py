@@ -9,7 +9,8 @@ among many short ones) -, a share of empty rows or columns, D and Dv of 1 .. 140
 integer or boolean mask values, now and then a scale, a stored zero, an infinity or a NaN among the mask values - and the mask
 as a COO, a COO built unsorted, a CSR or a CSC; the operands as NumPy arrays, device tensors or row-strided device views; in
 half of the cases an additive bias, shared or per head, with -inf entries in some: dbias is then compared too, in the order of
-the array the caller holds.  Prints one line per case; exits 1 at the first difference."""
+the array the caller holds; in half of the cases a dropout of 0.1 to 0.9 under a 64-bit seed (the restatement of
+tests/attention_dropout_cases.py then).  Prints one line per case; exits 1 at the first difference."""
 import argparse
 import os
 import sys
@@ -21,6 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import attention_bias_cases as bc  # noqa: E402
+import attention_dropout_cases as dc  # noqa: E402
 import attention_cases as ac  # noqa: E402
 import attention_grad_cases as gc  # noqa: E402
 import softmax_cases as sc  # noqa: E402
@@ -95,16 +97,24 @@ def main():
         given = None if bias is None else np.ascontiguousarray(bias[..., order])
         if given is not None and how != "numpy":
             given = torch.from_numpy(given).to("cuda:0")
-        outs = sparse_amd.sparse_attention_grad(s, *ops, scale=scale, bias=given)
+        drng = np.random.default_rng([a.seed, case, 2])                     # (a stream of its own again)
+        drop = {}
+        if drng.random() < 0.5:                                              # dropout in half of the cases
+            drop = dict(dropout=float(drng.choice([0.1, 0.5, 0.6, 0.9])), seed=int(drng.integers(0, 1 << 64, dtype=np.uint64)))
+        outs = sparse_amd.sparse_attention_grad(s, *ops, scale=scale, bias=given, **drop)
         outs = [o if isinstance(o, np.ndarray) else o.cpu().numpy() for o in outs]
-        want = gc.grad_heads(indptr, indices, vals, q, k, v, g, chunk, scale)
-        if bias is not None:
+        if drop:
+            want = dc.grad_dropout_heads(indptr, indices, vals, q, k, v, g, chunk, scale, bias, drop["dropout"], drop["seed"])
+            want = want[:3] if bias is None else want[:3] + (want[3][..., order],)
+        elif bias is None:
+            want = gc.grad_heads(indptr, indices, vals, q, k, v, g, chunk, scale)
+        else:
             want = bc.grad_bias_heads(indptr, indices, vals, q, k, v, g, chunk, scale, bias)
             want = want[:3] + (want[3][..., order],)
         ok = len(outs) == len(want) and all(sc.same_bits(o, w) for o, w in zip(outs, want))
         longest_col = int(np.bincount(np.asarray(indices, dtype=np.int64), minlength=1).max()) if len(vals) else 0
         print(f"case {case}: {np.dtype(dtype)} mask {np.dtype(mdt)} {np.dtype(idx)} {layout} {how} chunk {chunk} groups {group}/{col_group} "
-              f"scale {scale} bias {None if bias is None else bias.shape} D {D} Dv {Dv} heads {lead} shape {shape} nnz {len(vals)} longest row {int(np.diff(indptr).max())} "
+              f"scale {scale} bias {None if bias is None else bias.shape} dropout {drop.get('dropout')} D {D} Dv {Dv} heads {lead} shape {shape} nnz {len(vals)} longest row {int(np.diff(indptr).max())} "
               f"column {longest_col}: {'same bits' if ok else 'DIFFERENT'}", flush=True)
         if not ok:
             raise SystemExit(1)
