@@ -1005,6 +1005,49 @@ int spamd_attention_grad_dropout(int val_dtype, int idx_dtype, int64_t M, int64_
                                  const void* bias, int64_t bias_head, void* dbias, double rate, int64_t seed, int64_t head0,
                                  void* ws, int64_t ws_bytes, void* dq, void* dk, void* dv, void* stream);
 
+/* =======================================================================================
+ * A17  semiring products sparse @ dense -> dense (csrc/semiring_spmm.hip): the "add" is min or max, the "mul" plus or times,
+ *     out[i, j] = min | max over the stored (i, k) of   a[i, k] + b[k, j]   |   a[i, k] * b[k, j]
+ *     arg[i, j] = the k that was picked (int64; the argument a backward pass scatters through), -1 for none
+ *   - GraphBLAS mxm over the (min | max, plus | times) semirings with a dense right operand: max / min neighbourhood
+ *   aggregation, one Bellman-Ford relaxation (min.+), Viterbi (max.+), most-reliable path (max.x).  An unstored position is
+ *   ABSENT (not the value 0); a stored zero takes part as the value 0.
+ *   a comes as CSR: a_ptr (idx_dtype I32 | I64, M + 1 entries ascending from 0 to nnz), a_idx (inner indices below K, same type),
+ *   a_val (val_dtype F32 | F64 | I32 | I64, nnz values).  b (K x N), init (M x N, may be NULL), out (M x N) are of val_dtype
+ *   with row pitches ldb, ldi, ldo in elements (>= N), last axis contiguous; arg (int64, M x N, pitch lda) may be NULL - the
+ *   kernels without it carry no arg registers and make no arg stores.  init is only read.
+ *   Contract, for output (i, j) of a MIN semiring (MAX mirrored): with the stored elements of row i in stored order,
+ *   e = 0 .. n - 1, inner indices k_e,
+ *     t_e   = a[i, k_e] + b[k_e, j] (one add) or a[i, k_e] * b[k_e, j] (one multiply); integers wrap in two's complement (the
+ *             operation is done on the unsigned type)
+ *     seq   = [init[i, j]] (only when an init is given) followed by t_0 .. t_{n-1}
+ *     pick  = the element numpy.argmin picks on seq: the first NaN if there is one, else the FIRST element that attains the
+ *             minimum; -0.0 and +0.0 compare equal, so the first of them wins and keeps its sign bit
+ *     out   = its value (the payload and sign of a NaN are no result); arg = its k_e, or -1 when the init was picked
+ *   An empty seq (a row without stored elements and no init) gives the identity of the add - +inf / -inf, the integer type's
+ *   max / min - and arg -1.  "First NaN, else leftmost minimum" of the pieces of any in-order split, combined left to right, is
+ *   that of the whole: the result depends neither on narrow / group / chunk / max_len nor on the launch geometry.  No atomic
+ *   touches a value or an arg; every output is written exactly once.
+ *   add: SPAMD_SEMIRING_MIN | _MAX; mul: SPAMD_SEMIRING_PLUS | _TIMES.  narrow != 0: the lanes run ALONG a row, `group` of them
+ *   per output element (results of few columns; the matrix-vector product), else `group` lanes own a row and each lane 16 bytes
+ *   of contiguous output columns.  group: 8 | 16 | 32 | 64.  Rows longer than `chunk` (a multiple of 64 in 64 .. 2^30) are cut
+ *   into pieces of `chunk` elements whose states go to the workspace and are folded in piece order by a second launch that
+ *   starts after the first has ended.  max_len: the longest row's length, 0 .. nnz; it only decides whether the piece launches
+ *   are made.  ws: spamd_semiring_spmm_ws_bytes(val_dtype, nnz, N, chunk, arg != NULL) bytes (0 when nnz <= chunk), needed
+ *   when max_len > chunk (SPAMD_EWS).  The arrays are trusted, as by every entry point.
+ *   Returns before any launch: SPAMD_ETYPE for other type codes; SPAMD_EINVAL for other add / mul codes, negative sizes,
+ *   max_len > nnz, group / chunk outside the above, a pitch below N, null pointers with work to do; 0 for M == 0 or N == 0.
+ * ------------------------------------------------------------------------------------- */
+#define SPAMD_SEMIRING_MIN 0
+#define SPAMD_SEMIRING_MAX 1
+#define SPAMD_SEMIRING_PLUS 0
+#define SPAMD_SEMIRING_TIMES 1
+int64_t spamd_semiring_spmm_ws_bytes(int val_dtype, int64_t nnz, int64_t N, int64_t chunk, int with_arg);
+int spamd_semiring_spmm(int val_dtype, int idx_dtype, int add, int mul, int64_t M, int64_t K, int64_t N, int64_t nnz,
+                        const void* a_ptr, const void* a_idx, const void* a_val, const void* b, int64_t ldb, const void* init,
+                        int64_t ldi, int narrow, int group, int64_t chunk, int64_t max_len, void* ws, int64_t ws_bytes, void* out,
+                        int64_t ldo, int64_t* arg, int64_t lda, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1973,6 +1973,113 @@ def attention_grad_rows(indptr, indices, svals, colptr, colperm, colrows, q, k, 
 
 
 # ---------------------------------------------------------------------------------------------
+# semiring products sparse @ dense (csrc/semiring_spmm.hip)
+# ---------------------------------------------------------------------------------------------
+SEMIRING_ADDS = ("min", "max")
+SEMIRING_MULS = ("plus", "times")
+SEMIRING_DTYPES = (torch.float32, torch.float64, torch.int32, torch.int64)
+SEMIRING_GROUPS = (8, 16, 32, 64)
+SEMIRING_FORMS = ("rows", "lanes", "long")
+SEMIRING_MAX_CHUNK = 1 << 30     # SR_MAX_CHUNK of csrc/semiring_spmm.hip
+# None of these changes a bit of the result (include/sparse_amd.h A17: the rule is associative over any in-order split).
+# SEMIRING_LANES_MAX_N: results of at most that many columns run the lanes ALONG the rows ("lanes"), wider ones give every lane
+# 16 bytes of output columns ("rows").  SEMIRING_CHUNK: rows longer than it are cut into pieces ("long").  The sub-group width
+# defaults to the narrowest that covers the result's columns with 16 bytes a lane ("rows") or that takes a mean row in one trip
+# of four elements a lane ("lanes").  Chosen with tools/semiring_time.py --sweep (MI355X, float32, ms per call of this wrapper,
+# median of 5 rounds of 20 calls, the alternatives taking turns in one process, min-max spread below 4 %), run with these
+# defaults in place: (a) CSR graph of 2^17 nodes, mean degree 32, N = 64, max.times; (b) the same graph, N = 1, min.plus with an
+# init; (c) one hub row of 10^6 among 2^16 rows of 8, N = 16, max.times:
+#   group            8       16      32      64
+#     (a) rows     0.2050  0.1665  0.2304  0.3732     16 lanes x 16 bytes = the 64 columns: the default's choice
+#     (b) lanes    0.0259  0.0287  0.0423  0.0732     8 lanes x 4 elements = a mean row: the default's choice
+#     (b) rows     0.0614  0.0948  0.1590  0.2735     (the other form at each size, for the record)
+#     (a) lanes    0.5751  1.1970  2.2296  3.6593
+#   N (graph of (a))   1       2       3       4       5       6       8       16      (each form at its default width)
+#     rows           0.0629  0.0609  0.0616  0.0708  0.0651  0.0702  0.0842  0.0938
+#     lanes          0.0261  0.0304  0.0395  0.0453  0.0570  0.0665  0.0858  0.1659
+#       lanes lead by 2.4 x at 1 and still 1.56 x at 4, by 12 % at 5 and 5 % at 6, and lose from 8 on (7: not measured).  The cut-off
+#       is 4: up to there the lead is large; the small one at 5 and 6 is that of one graph of one degree and one value type
+#   chunk            64      256     512     1024    2048    4096    16384
+#     (c)          1.5966  0.4367  0.2555  0.1809  0.1684  0.2384  0.7973    short pieces: more windows; long ones: too few waves
+SEMIRING_LANES_MAX_N = 4
+SEMIRING_CHUNK = 2048
+
+
+def _semiring_group(narrow, N, itemsize, nnz, M):
+    """the default sub-group width: "rows" - the narrowest whose lanes, 16 bytes of columns each, cover the N columns; "lanes" -
+    the narrowest that takes a mean row in one trip of four elements a lane"""
+    want = -(-nnz // max(4 * M, 1)) if narrow else -(-N * itemsize // 16)
+    return next((g for g in SEMIRING_GROUPS if g >= want), 64)
+
+
+def _pitched2(t):
+    """(2-D tensor whose last axis is contiguous, row pitch in elements): a view where the strides allow it, else one copy"""
+    rows, width = int(t.shape[0]), int(t.shape[1])
+    if width > 1 and t.stride(1) != 1 or rows > 1 and t.stride(0) < width:
+        t = t.contiguous()
+    return t, (int(t.stride(0)) if rows > 1 else width)
+
+
+def semiring_spmm(indptr, indices, vals, b, max_len, *, add, mul, init=None, return_arg=False, form=None, group=None, chunk=None):
+    """out[i, j] = (min | max) over the stored (i, k) of vals[i, k] (+ | *) b[k, j] for the CSR matrix (`vals`, `indices`, `indptr`:
+    M + 1 int32 | int64 pointers) (spamd_semiring_spmm).  `b` [K, N] or [K] is a device tensor of the type of `vals` (float32,
+    float64, int32 or int64; any strides: a row pitch is passed through), `init` None or a tensor of the result's shape and
+    type that every output starts from (it is only read), `max_len` the longest row's length.  Returns the dense [M, N] or [M]
+    tensor; with `return_arg` (out, arg), arg int64: the k that was picked, -1 for the init or an empty row.
+    `form` forces a kernel form, for tests and sweeps: "rows" (`group` lanes own a row, 16 bytes of columns a lane), "lanes"
+    (`group` lanes run along a row, per output element) - both without pieces unless a `chunk` is given -, "long" (pieces of
+    `chunk`, default 64 here, for the rows longer than it); `group` and `chunk` never change a bit."""
+    if add not in SEMIRING_ADDS or mul not in SEMIRING_MULS:
+        raise ValueError(f"semiring_spmm: add must be one of {SEMIRING_ADDS} and mul one of {SEMIRING_MULS} (the semirings min.plus, "
+                         f"min.times, max.plus and max.times), got add={add!r}, mul={mul!r}")
+    if form not in (None,) + SEMIRING_FORMS:
+        raise ValueError(f"semiring_spmm: form must be one of {SEMIRING_FORMS} or None, got {form!r}")
+    if group is not None and group not in SEMIRING_GROUPS:
+        raise ValueError(f"semiring_spmm: group must be one of {SEMIRING_GROUPS} or None, got {group!r}")
+    if chunk is not None and (int(chunk) != chunk or chunk < 64 or chunk > SEMIRING_MAX_CHUNK or chunk % 64):
+        raise ValueError(f"semiring_spmm: chunk must be a multiple of 64 in 64 .. {SEMIRING_MAX_CHUNK} or None, got {chunk!r}")
+    dt = b.dtype
+    if dt not in SEMIRING_DTYPES or vals.dtype != dt or (init is not None and init.dtype != dt):
+        raise TypeError("semiring_spmm: the values, b and the init must all be float32, float64, int32 or int64 - one type")
+    if not index_dtype_ok(indptr) or indices.dtype != indptr.dtype:
+        raise TypeError("semiring_spmm: indptr and indices must both be int32 or both int64")
+    if b.ndim not in (1, 2):
+        raise ValueError(f"semiring_spmm: b must have 1 or 2 dimensions, got {b.ndim}")
+    M, K, nnz, max_len = int(indptr.numel()) - 1, int(b.shape[0]), int(vals.numel()), int(max_len)
+    out_shape = (M,) if b.ndim == 1 else (M, int(b.shape[1]))
+    if M < 0 or int(indices.numel()) != nnz or (nnz and K == 0):
+        raise ValueError("semiring_spmm: shape mismatch between the CSR arrays and b")
+    if init is not None and tuple(int(n) for n in init.shape) != out_shape:
+        raise ValueError(f"semiring_spmm: the init must have the result's shape {out_shape}, got {tuple(init.shape)}")
+    dev = require_hip(indptr, indices, vals, b, init)
+    N = out_shape[1] if b.ndim == 2 else 1
+    if M == 0 or N == 0 or nnz == 0:      # nothing to fold: the init, or the identity of the add - no launch
+        if init is not None:
+            out = init.clone(memory_format=torch.contiguous_format)
+        else:
+            lim = torch.finfo(dt) if dt.is_floating_point else torch.iinfo(dt)
+            top = float("inf") if dt.is_floating_point else lim.max
+            out = torch.full(out_shape, (top if add == "min" else (-top if dt.is_floating_point else lim.min)), dtype=dt, device=dev)
+        return (out, torch.full(out_shape, -1, dtype=torch.int64, device=dev)) if return_arg else out
+    narrow = N <= SEMIRING_LANES_MAX_N if form in (None, "long") else form == "lanes"
+    chunk = (64 if form == "long" else SEMIRING_CHUNK if form is None else SEMIRING_MAX_CHUNK) if chunk is None else int(chunk)
+    group = _semiring_group(narrow, N, b.element_size(), nnz, M) if group is None else int(group)
+    b2, ldb = _pitched2(b if b.ndim == 2 else b.unsqueeze(1))
+    i2, ldi = (None, N) if init is None else _pitched2(init if b.ndim == 2 else init.unsqueeze(1))
+    out = torch.empty((M, N), dtype=dt, device=dev)
+    arg = torch.empty((M, N), dtype=torch.int64, device=dev) if return_arg else None
+    ws_bytes = int(_ffi.lib().spamd_semiring_spmm_ws_bytes(code_of(dt), nnz, N, chunk, int(return_arg))) if max_len > chunk else 0
+    if ws_bytes < 0:
+        raise _ffi.HipBackendError(f"spamd_semiring_spmm_ws_bytes failed: {ws_bytes}")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    _ffi.call("spamd_semiring_spmm", code_of(dt), code_of(indptr.dtype), SEMIRING_ADDS.index(add), SEMIRING_MULS.index(mul), M, K, N,
+              nnz, ptr(indptr.contiguous()), ptr(indices.contiguous()), ptr(vals.contiguous()), ptr(b2), ldb, ptr(i2), ldi,
+              int(narrow), group, chunk, max_len, ptr(ws), ws_bytes, ptr(out), N, ptr(arg), N, stream_ptr(dev))
+    out, arg = out.reshape(out_shape), (arg.reshape(out_shape) if return_arg else None)
+    return (out, arg) if return_arg else out
+
+
+# ---------------------------------------------------------------------------------------------
 # masked SpGEMM (csrc/masked_spgemm.hip)
 # ---------------------------------------------------------------------------------------------
 MASKED_DTYPES = (torch.float32, torch.float64, torch.int32, torch.int64)
