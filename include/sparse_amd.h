@@ -1048,6 +1048,55 @@ int spamd_semiring_spmm(int val_dtype, int idx_dtype, int add, int mul, int64_t 
                         int64_t ldi, int narrow, int group, int64_t chunk, int64_t max_len, void* ws, int64_t ws_bytes, void* out,
                         int64_t ldo, int64_t* arg, int64_t lda, void* stream);
 
+/* =======================================================================================
+ * A18  the backward pass of A17 (csrc/semiring_grad.hip): from g = d loss / d out (M x N) and the forward's arg (M x N, int64),
+ *   da (nnz values: the gradient with respect to a_val, in CSR stored order), db (K x N) and dinit (M x N).  Only arg is needed,
+ *   not the add.  a_ptr / a_idx / a_val, b, mul, M, K, N, nnz are A17's; val_dtype is F32 | F64 (min / max of integers has no
+ *   gradient here: SPAMD_ETYPE).  c_ptr (idx_dtype, K + 1 entries), c_perm (int64[nnz]) and c_row (idx_dtype, nnz) are the
+ *   column grouping of the pattern exactly as A16 defines it.  b, arg, g, db and dinit have row pitches ldb, lda, ldg, lddb, lddi
+ *   in elements (>= N), last axis contiguous; da is contiguous.  Nothing but da, db, dinit and ws is written.
+ *   For output (i, j) with k* = arg[i][j]: k* == -1 - the init or the identity was picked - credits no element of a or b, and
+ *   dinit[i][j] = g[i][j].  Otherwise the CREDITED elements are the stored elements e of row i with k_e == k*: exactly one in a
+ *   pattern without duplicate coordinates; with duplicates every one of them is credited (this is not detected).  On a tie the
+ *   element the forward picked gets everything - the subgradient torch.max(dim=..) takes.  For plus d t / d a_e = 1 and
+ *   d t / d b[k][j] = 1; for times d t / d a_e = b[k_e][j] and d t / d b[k_e][j] = a_e.  arg is only ever COMPARED with stored
+ *   indices, never used as an address: a value that is no index of row i credits nothing.
+ *   Contract, with hit(e, j) = (arg[i_e][j] == k_e): every operation is rounded once (an fma counts as one); every output
+ *   element is written exactly once; no atomic touches a value; the result depends neither on group / col_group / short_max /
+ *   max_col nor on the launch geometry (`chunk` is part of the order of db, as in A16).
+ *     da[e], element e of row i, k = k_e, by A15's 64 accumulators over the N columns: accumulator l starts at +0.0 and takes
+ *             j = l, l + 64, l + 128, .. in ascending order; on a hit a_l = a_l + g[i][j] (plus) or a_l = fma(g[i][j], b[k][j], a_l)
+ *             (times), on no hit a_l is unchanged; the 64 accumulators are then folded by halving, h = 32 .. 1.  da[e] depends on
+ *             its own row of arg / g and its own b row alone: there is no long-row form, the pass runs over windows of stored
+ *             positions
+ *     db[k][j], column k, its stored elements in stored order: positions pos_0 < .. < pos_{m-1} with rows r_i from c_ptr /
+ *             c_perm / c_row, cut into pieces of `chunk` elements by A16's rule; a piece starts at +0.0; on a hit at (pos_i, j)
+ *             acc = acc + g[r_i][j] (plus) or acc = fma(a_val[pos_i], g[r_i][j], acc) (times), on no hit acc is unchanged; the
+ *             piece sums are added in piece order, the first piece's sum being the start.  A column without stored elements
+ *             gives +0.0
+ *     dinit[i][j] = arg[i][j] == -1 ? g[i][j] : +0.0
+ *   NaN and infinity in g follow from the arithmetic and reach only credited elements (and, through dinit, the init).
+ *   Any of da, db, dinit may be NULL: the pass that serves only a NULL output is not launched (element pass: da; column pass:
+ *   db; one elementwise launch: dinit).  For plus neither a_val nor b is read and both may be NULL; the element pass reads
+ *   neither a_val nor the column grouping, the column pass neither a_ptr, a_idx nor b.
+ *   group (element pass): 8 | 16 | 32 | 64 lanes run along the columns of one stored element.  col_group (column pass):
+ *   8 | 16 | 32 | 64 lanes own a column of at most short_max (0 .. 64) elements, 16 bytes of contiguous output columns a lane;
+ *   col_group 1 (N <= 4 only): a lane owns all outputs of such a column.  Columns up to `chunk` (a multiple of 64 in
+ *   64 .. 2^30) elements take a wave each, longer ones pieces through the workspace and a join launch that starts after the
+ *   piece launch has ended: no workgroup waits for another.  max_col: the longest column, 0 .. nnz; it only decides which
+ *   launches are made.  ws: spamd_semiring_grad_ws_bytes(val_dtype, nnz, N, chunk) bytes (0 when nnz <= chunk), needed when db
+ *   is wanted and max_col > chunk (SPAMD_EWS).  The arrays are trusted, as by every entry point.
+ *   Returns before any launch: SPAMD_ETYPE for other type codes (the integer value types too); SPAMD_EINVAL for another mul
+ *   code, negative sizes, max_col > nnz, group / col_group / short_max / chunk outside the above, a pitch below N, null
+ *   pointers with work to do; SPAMD_EWS; 0 when da, db and dinit are all NULL or empty.
+ * ------------------------------------------------------------------------------------- */
+int64_t spamd_semiring_grad_ws_bytes(int val_dtype, int64_t nnz, int64_t N, int64_t chunk);
+int spamd_semiring_grad(int val_dtype, int idx_dtype, int mul, int64_t M, int64_t K, int64_t N, int64_t nnz, const void* a_ptr,
+                        const void* a_idx, const void* a_val, const void* c_ptr, const int64_t* c_perm, const void* c_row,
+                        const void* b, int64_t ldb, const int64_t* arg, int64_t lda, const void* g, int64_t ldg, int group,
+                        int col_group, int64_t short_max, int64_t chunk, int64_t max_col, void* ws, int64_t ws_bytes, void* da,
+                        void* db, int64_t lddb, void* dinit, int64_t lddi, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,7 +39,7 @@ from ._mttkrp import mttkrp
 from ._softmax import softmax
 from ._attention import sparse_attention, sparse_attention_autograd, sparse_attention_grad, sparse_attention_keep_mask
 from ._masked import masked_matmul
-from ._semiring import semiring_matmul
+from ._semiring import semiring_matmul, semiring_matmul_autograd, semiring_matmul_grad
 from ._api import (all, any, argwhere, asarray, astype, empty, empty_like, expand_dims, eye, full, full_like,
                    matrix_transpose, max, mean, min, moveaxis, nanmax, nanmean, nanmin, nanprod, nanreduce, nansum, nonzero,
                    ones, ones_like, permute_dims, prod, random, reshape, sddmm, squeeze, std, sum, var, vecdot, where, zeros,
@@ -65,5 +65,5 @@ __all__ = ["COO", "GCXS", "SparseArray", "HipBackendError", "abs", "acos", "acos
            "square", "subtract", "tan", "tanh", "sort", "tril", "triu", "trunc", "uint16", "uint32", "uint64", "uint8", 
            "concatenate", "dot", "einsum", "elemwise", "empty", "empty_like", "expand_dims", "eye", "full", "full_like", "load_npz", "matmul",
            "matrix_transpose", "max", "mean", "min", "moveaxis", "nanmax", "nanmean", "nanmin", "nanprod", "nanreduce", "nansum",
-           "nonzero", "ones", "ones_like", "permute_dims", "prod", "random", "reshape", "save_npz", "sddmm", "semiring_matmul", "softmax", "sparse_attention", "sparse_attention_autograd", "sparse_attention_grad", "sparse_attention_keep_mask", "squeeze", "stack", "std",
+           "nonzero", "ones", "ones_like", "permute_dims", "prod", "random", "reshape", "save_npz", "sddmm", "semiring_matmul", "semiring_matmul_autograd", "semiring_matmul_grad", "softmax", "sparse_attention", "sparse_attention_autograd", "sparse_attention_grad", "sparse_attention_keep_mask", "squeeze", "stack", "std",
            "sum", "tensordot", "var", "vecdot", "where", "zeros", "zeros_like"]

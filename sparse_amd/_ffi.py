@@ -198,6 +198,9 @@ SIGNATURES = {
     "spamd_semiring_spmm_ws_bytes": (_i64, [_int, _i64, _i64, _i64, _int]),
     "spamd_semiring_spmm": (_int, [_int, _int, _int, _int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _int, _int,
                                    _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "spamd_semiring_grad_ws_bytes": (_i64, [_int, _i64, _i64, _i64]),
+    "spamd_semiring_grad": (_int, [_int, _int, _int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
+                                   _i64, _int, _int, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp]),
     "spamd_spmm_csr_stream_fits":(_int, [_int, _i64, _i64, _i64, _vp, _vp]),
     "spamd_spmm_csr_stream_passes": (_int, [_int, _i64, _i64, _i64, _vp, _vp, _u32]),
     "spamd_spmm_csr_ldsb_fits": (_int, [_int, _i64, _i64, _i64, _vp, _i64, _vp, _i64]),

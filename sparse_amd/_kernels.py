@@ -2079,6 +2079,131 @@ def semiring_spmm(indptr, indices, vals, b, max_len, *, add, mul, init=None, ret
     return (out, arg) if return_arg else out
 
 
+# ---- the backward pass (csrc/semiring_grad.hip) ----
+SEMIRING_GRAD_COL_FORMS = ("short", "wide", "long")
+SEMIRING_GRAD_COL_GROUPS = (1,) + SEMIRING_GROUPS      # 1: a lane owns all outputs of a column (results of at most 4 columns)
+SEMIRING_GRAD_LANE_MAX_N = 4                           # SG_LANE_MAX_N of csrc/semiring_grad.hip
+# None of these changes a bit of da or dinit; db depends on `chunk` alone (include/sparse_amd.h A18: the piece rule is part of
+# the order, as in A16).  Chosen with tools/semiring_grad_time.py --sweep (MI355X, float32, ms per call of this wrapper, median of
+# 5 rounds of 20 calls, the alternatives taking turns in one process, min-max spread below 2 %; one parameter at a time, the
+# others at A16's column defaults - col_group 32, short_max 64, chunk 1024 - and A17's width rule for the element pass): (a) CSR
+# graph of 2^17 nodes, mean degree 32, N = 64, max.times; (b) the same graph, N = 1, min.plus with an init; (c) one hub COLUMN of
+# 10^6 among 10^6 rows, N = 16, max.times:
+#   group (element pass alone)      8       16      32      64
+#     (a)                         0.1439  0.1920  0.3131  0.5463     8 lanes x 8 accumulators: the narrowest wins at every size,
+#     (b)                         0.0748  0.1157  0.2144  0.4082     more elements in flight per wave
+#     (c)                         0.0677  0.0880  0.1555  0.2822
+#   col_group (column pass alone)   1       8       16      32      64
+#     (a)                                 0.6038  0.4995  0.4993  0.5735     16 lanes x 16 bytes = the 64 columns
+#     (b)                         0.0397  0.1185  0.1962  0.3444  0.6005     a lane per column: 3 x the narrowest sub-group
+#     (c)                                 0.5556  0.5674  0.5834  0.6130     (the hub column's pieces dominate)
+#   short_max (column pass alone)   0       8       16      32      64
+#     (a)                         0.5869  0.5867  0.5915  0.5891  0.4994
+#     (b)                         0.6026  0.6023  0.6065  0.3740  0.0398
+#     (c)                         0.6085  0.5822  0.5830  0.5831  0.5831
+#   chunk (column pass alone)       64      256     512     1024    2048    4096    16384
+#     (c)                         4.954   1.390   0.795   0.583   0.669   1.116   4.118     short pieces: more windows; long: too few waves
+# Shipped: group 8; col_group 1 for results of at most 4 columns, else the narrowest sub-group whose lanes, 16 bytes of columns
+# each, cover the N columns (A17's rule for its rows form: 16 at (a), 8 at (c) - the fastest or within 0.1 % of it at both);
+# short_max 64 and chunk 1024 (A16's).
+SEMIRING_GRAD_GROUP = 8
+SEMIRING_GRAD_SHORT_MAX = ATTENTION_GRAD_SHORT_MAX
+SEMIRING_GRAD_CHUNK = 1024
+SEMIRING_GRAD_STATS = {}      # the passes of the last call that reached the entry (tests): {"da", "db", "dinit"} -> bool
+
+
+def _semiring_grad_col_group(N, itemsize):
+    """the default width of the column pass: a lane per column for results of at most 4 columns, else A17's rule for the rows form"""
+    return 1 if N <= SEMIRING_GRAD_LANE_MAX_N else _semiring_group(False, N, itemsize, 0, 1)
+
+
+def semiring_grad(indptr, indices, vals, colptr, colperm, colrows, b, arg, g, max_col, *, mul, want=(True, True, False),
+                  col_form=None, group=None, col_group=None, short_max=None, chunk=None):
+    """(da, db, dinit) of `semiring_spmm` for the gradient `g` of its result and the forward's `arg` (spamd_semiring_grad): da
+    [nnz] in the order of `vals`, db of the shape of `b`, dinit of the shape of `g`; `want` = (da?, db?, dinit?) - an output that
+    is not wanted is None and its pass is not launched.  The CSR matrix, `b` and `mul` are those of `semiring_spmm` (float32 /
+    float64 only); `arg` is int64, `arg` and `g` have the result's shape, any strides.  `colptr` (K + 1, the type of `indptr`),
+    `colperm` (int64[nnz]) and `colrows` (nnz, the type of `indptr`) are the column grouping of `attention_grad_rows`, `max_col`
+    the longest column; all four may be None when db is not wanted.  For "plus" `vals` is not read.
+    `col_form` forces a form on the column pass, for tests and sweeps: "short" (sub-groups of `col_group` lanes; at most 64
+    elements a column), "wide" (a wave each; at most `chunk`), "long" (a wave up to `chunk`, default 64 here, pieces beyond);
+    `short_max` moves the length at which a column goes from a sub-group to a wave; `group` is the width of the element pass,
+    `col_group` 1 gives a lane a whole column's outputs (N <= 4)."""
+    if mul not in SEMIRING_MULS:
+        raise ValueError(f"semiring_grad: mul must be one of {SEMIRING_MULS}, got {mul!r}")
+    if col_form not in (None,) + SEMIRING_GRAD_COL_FORMS:
+        raise ValueError(f"semiring_grad: col_form must be one of {SEMIRING_GRAD_COL_FORMS} or None, got {col_form!r}")
+    if group is not None and group not in SEMIRING_GROUPS:
+        raise ValueError(f"semiring_grad: group must be one of {SEMIRING_GROUPS} or None, got {group!r}")
+    if col_group is not None and col_group not in SEMIRING_GRAD_COL_GROUPS:
+        raise ValueError(f"semiring_grad: col_group must be one of {SEMIRING_GRAD_COL_GROUPS} or None, got {col_group!r}")
+    if short_max is not None and (int(short_max) != short_max or short_max < 0 or short_max > 64):
+        raise ValueError(f"semiring_grad: short_max must lie in 0 .. 64 or be None, got {short_max!r}")
+    if chunk is not None and (int(chunk) != chunk or chunk < 64 or chunk > SEMIRING_MAX_CHUNK or chunk % 64):
+        raise ValueError(f"semiring_grad: chunk must be a multiple of 64 in 64 .. {SEMIRING_MAX_CHUNK} or None, got {chunk!r}")
+    want_da, want_db, want_di = (bool(w) for w in want)
+    dt = b.dtype
+    if dt in (torch.int32, torch.int64):
+        raise TypeError("semiring_grad: min / max of integers has no gradient here - the values, b and g must be float32 or float64")
+    if dt not in (torch.float32, torch.float64) or vals.dtype != dt or g.dtype != dt:
+        raise TypeError("semiring_grad: the values, b and g must all be float32 or all float64 - one type")
+    if arg.dtype != torch.int64:
+        raise TypeError(f"semiring_grad: arg must be int64, got {arg.dtype}")
+    if not index_dtype_ok(indptr) or indices.dtype != indptr.dtype:
+        raise TypeError("semiring_grad: indptr and indices must both be int32 or both int64")
+    if want_db and (colptr is None or colperm is None or colrows is None or colptr.dtype != indptr.dtype
+                    or colrows.dtype != indptr.dtype or colperm.dtype != torch.int64):
+        raise TypeError("semiring_grad: db needs the column grouping: colptr and colrows of the type of indptr, colperm int64")
+    if b.ndim not in (1, 2):
+        raise ValueError(f"semiring_grad: b must have 1 or 2 dimensions, got {b.ndim}")
+    M, K, nnz = int(indptr.numel()) - 1, int(b.shape[0]), int(vals.numel())
+    out_shape = (M,) if b.ndim == 1 else (M, int(b.shape[1]))
+    N = out_shape[1] if b.ndim == 2 else 1
+    if M < 0 or int(indices.numel()) != nnz or (nnz and K == 0):
+        raise ValueError("semiring_grad: shape mismatch between the CSR arrays and b")
+    if tuple(int(n) for n in arg.shape) != out_shape or tuple(int(n) for n in g.shape) != out_shape:
+        raise ValueError(f"semiring_grad: arg and g must have the result's shape {out_shape}, got {tuple(arg.shape)} and {tuple(g.shape)}")
+    if want_db and (int(colptr.numel()) != K + 1 or int(colperm.numel()) != nnz or int(colrows.numel()) != nnz):
+        raise ValueError("semiring_grad: shape mismatch between the column grouping, the CSR arrays and b")
+    max_col = int(max_col or 0)
+    chunk = (64 if col_form == "long" else SEMIRING_GRAD_CHUNK) if chunk is None else int(chunk)
+    short_max = (SEMIRING_GRAD_SHORT_MAX if short_max is None else int(short_max)) if col_form in (None, "short") else 0
+    if want_db and (col_form == "short" and max_col > 64 or col_form == "wide" and max_col > chunk):
+        raise ValueError(f"semiring_grad: col_form {col_form!r} does not take a column of {max_col} elements")
+    if col_group is None:
+        col_group = _semiring_grad_col_group(N, b.element_size())
+    elif col_group == 1 and N > SEMIRING_GRAD_LANE_MAX_N:
+        raise ValueError(f"semiring_grad: col_group 1 takes results of at most {SEMIRING_GRAD_LANE_MAX_N} columns, got {N}")
+    group = SEMIRING_GRAD_GROUP if group is None else int(group)
+    dev = require_hip(indptr, indices, vals, b, arg, g, *((colptr, colperm, colrows) if want_db else ()))
+    SEMIRING_GRAD_STATS.clear()
+    SEMIRING_GRAD_STATS.update(da=False, db=False, dinit=False)
+    if M == 0 or N == 0 or nnz == 0 or K == 0:      # nothing is credited: no launch
+        return (torch.zeros(nnz, dtype=dt, device=dev) if want_da else None,
+                torch.zeros(tuple(b.shape), dtype=dt, device=dev) if want_db else None,
+                g.clone(memory_format=torch.contiguous_format) if want_di else None)
+    if not (want_da or want_db or want_di):
+        return None, None, None
+    times = mul == "times"
+    b2, ldb = _pitched2(b if b.ndim == 2 else b.unsqueeze(1)) if times and want_da else (None, N)
+    a2, lda = _pitched2(arg if b.ndim == 2 else arg.unsqueeze(1))
+    g2, ldg = _pitched2(g if b.ndim == 2 else g.unsqueeze(1))
+    da = torch.empty(nnz, dtype=dt, device=dev) if want_da else None
+    db = torch.empty((K, N), dtype=dt, device=dev) if want_db else None
+    di = torch.empty((M, N), dtype=dt, device=dev) if want_di else None
+    ws_bytes = int(_ffi.lib().spamd_semiring_grad_ws_bytes(code_of(dt), nnz, N, chunk)) if want_db and max_col > chunk else 0
+    if ws_bytes < 0:
+        raise _ffi.HipBackendError(f"spamd_semiring_grad_ws_bytes failed: {ws_bytes}")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    cp, cm, cr = (colptr.contiguous(), colperm.contiguous(), colrows.contiguous()) if want_db else (None, None, None)
+    SEMIRING_GRAD_STATS.update(da=want_da, db=want_db, dinit=want_di)
+    _ffi.call("spamd_semiring_grad", code_of(dt), code_of(indptr.dtype), SEMIRING_MULS.index(mul), M, K, N, nnz, ptr(indptr.contiguous()),
+              ptr(indices.contiguous()), ptr(vals.contiguous()) if times and want_db else None, ptr(cp), ptr(cm), ptr(cr), ptr(b2), ldb,
+              ptr(a2), lda, ptr(g2), ldg, group, col_group, short_max, chunk, max_col if want_db else 0, ptr(ws), ws_bytes, ptr(da),
+              ptr(db), N, ptr(di), N, stream_ptr(dev))
+    return da, (db.reshape(tuple(b.shape)) if want_db else None), (di.reshape(out_shape) if want_di else None)
+
+
 # ---------------------------------------------------------------------------------------------
 # masked SpGEMM (csrc/masked_spgemm.hip)
 # ---------------------------------------------------------------------------------------------
