@@ -1576,6 +1576,32 @@ def sddmm_fold(coords, nlead, a_strides, b_strides, M, N, rows_total, cols_total
 
 
 # ---------------------------------------------------------------------------------------------
+# what the wrappers of the segment walkers share (DESIGN.md "The shared segment walk")
+# ---------------------------------------------------------------------------------------------
+def _seg_forms(what, form, chunk, short_max, longest, default_chunk, default_short_max, kind, name="form"):
+    """(chunk, short_max) of a call with the forced `form` (None: the defaults; "long": pieces of 64 unless a chunk is given;
+    "wide" and "long": no sub-groups), or the error of a form that cannot take the `longest` segment"""
+    chunk = (64 if form == "long" else default_chunk) if chunk is None else int(chunk)
+    short_max = (default_short_max if short_max is None else int(short_max)) if form in (None, "short") else 0
+    if form == "short" and longest > 64 or form == "wide" and longest > chunk:
+        raise ValueError(f"{what}: {name} {form!r} does not take a {kind} of {longest} elements")
+    return chunk, short_max
+
+
+def _seg_scale(scale, dt):
+    """(has_scale, the scale rounded to the data type once) for the C entries"""
+    return (0, 0.0) if scale is None else (1, float(np.asarray(scale).astype(np_dtype(dt))))
+
+
+def _seg_workspace(entry, dev, *args):
+    """(workspace or None, its size) as the C entry `entry` (a spamd_*_ws_bytes) sizes it"""
+    ws_bytes = int(getattr(_ffi.lib(), entry)(*args))
+    if ws_bytes < 0:
+        raise _ffi.HipBackendError(f"{entry} failed: {ws_bytes}")
+    return (torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None), ws_bytes
+
+
+# ---------------------------------------------------------------------------------------------
 # MTTKRP (csrc/mttkrp.hip)
 # ---------------------------------------------------------------------------------------------
 MTTKRP_MAX_NDIM = 8      # MTTKRP_MAX_NDIM of csrc/mttkrp.hip
@@ -1638,10 +1664,7 @@ def mttkrp_coo(coords, data, shape, factors, mode, plan, *, chunk=None, exact=Fa
             f = f.contiguous()
             keep.append(f)
         fptr[d], pitch[d] = ptr(f), max(int(f.stride(0)), R) if f.shape[0] > 1 else R
-    ws_bytes = int(_ffi.lib().spamd_mttkrp_ws_bytes(code_of(dt), nnz, R, chunk))
-    if ws_bytes < 0:
-        raise _ffi.HipBackendError(f"spamd_mttkrp_ws_bytes failed: {ws_bytes}")
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    ws, ws_bytes = _seg_workspace("spamd_mttkrp_ws_bytes", dev, code_of(dt), nnz, R, chunk)
     _ffi.call("spamd_mttkrp", code_of(dt), code_of(coords.dtype), ndim, int(mode), nnz, R, ptr(coords), int(coords.stride(0)) if nnz else 0,
               ptr(data.contiguous()), (_ct.c_void_p * ndim)(*fptr), _harr64(pitch), ptr(plan.perm), ptr(plan.rowptr), nrows, chunk,
               ptr(ws), ws_bytes, ptr(out), R, _ffi.EXACT_MULADD if exact else 0, stream_ptr(dev))
@@ -1691,20 +1714,12 @@ def softmax_segments(segptr, perm, data, max_len, *, scale=None, group=None, chu
     nnz, nseg, max_len = int(data.numel()), int(segptr.numel()) - 1, int(max_len)
     if form not in (None,) + SOFTMAX_FORMS:
         raise ValueError(f"softmax: form must be one of {SOFTMAX_FORMS} or None, got {form!r}")
-    chunk = (64 if form == "long" else SOFTMAX_CHUNK) if chunk is None else int(chunk)
-    short_max = (SOFTMAX_SHORT_MAX if short_max is None else int(short_max)) if form in (None, "short") else 0
-    if form == "short" and max_len > 64 or form == "wide" and max_len > chunk:
-        raise ValueError(f"softmax: form {form!r} does not take a group of {max_len} elements")
+    chunk, short_max = _seg_forms("softmax", form, chunk, short_max, max_len, SOFTMAX_CHUNK, SOFTMAX_SHORT_MAX, "group")
     group = SOFTMAX_GROUP if group is None else int(group)
     out = torch.empty_like(data, memory_format=torch.contiguous_format)
-    ws_bytes = int(_ffi.lib().spamd_softmax_ws_bytes(code_of(dt), nnz, chunk)) if max_len > chunk else 0
-    if ws_bytes < 0:
-        raise _ffi.HipBackendError(f"spamd_softmax_ws_bytes failed: {ws_bytes}")
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
-    has_scale = scale is not None
-    sc = float(np.asarray(scale).astype(np_dtype(dt))) if has_scale else 0.0
+    ws, ws_bytes = _seg_workspace("spamd_softmax_ws_bytes", dev, code_of(dt), nnz, chunk) if max_len > chunk else (None, 0)
     _ffi.call("spamd_softmax", code_of(dt), code_of(segptr.dtype), nseg, nnz, ptr(segptr.contiguous()), ptr(perm),
-              ptr(data.contiguous()), int(has_scale), sc, group, short_max, chunk, max_len, ptr(ws), ws_bytes, ptr(out),
+              ptr(data.contiguous()), *_seg_scale(scale, dt), group, short_max, chunk, max_len, ptr(ws), ws_bytes, ptr(out),
               stream_ptr(dev))
     return out
 
@@ -1821,41 +1836,28 @@ def attention_rows(indptr, indices, svals, q, k, v, max_len, *, scale=None, grou
     nnz, max_len = int(svals.numel()), int(max_len)
     if form not in (None,) + ATTENTION_FORMS:
         raise ValueError(f"attention: form must be one of {ATTENTION_FORMS} or None, got {form!r}")
-    chunk = (64 if form == "long" else ATTENTION_CHUNK) if chunk is None else int(chunk)
-    short_max = (ATTENTION_SHORT_MAX if short_max is None else int(short_max)) if form in (None, "short") else 0
-    if form == "short" and max_len > 64 or form == "wide" and max_len > chunk:
-        raise ValueError(f"attention: form {form!r} does not take a row of {max_len} elements")
+    chunk, short_max = _seg_forms("attention", form, chunk, short_max, max_len, ATTENTION_CHUNK, ATTENTION_SHORT_MAX, "row")
     group = ATTENTION_GROUP if group is None else int(group)
     q3, qp, qh = _rows3(q, dev)
     k3, kp, kh = _rows3(k, dev)
     v3, vp, vh = _rows3(v, dev)
     H = int(q3.shape[0])
     out = torch.empty(lead + (M, Dv), dtype=dt, device=dev)
-    ws_bytes = int(_ffi.lib().spamd_attention_ws_bytes(code_of(dt), nnz, H, Dv, chunk)) if max_len > chunk else 0
-    if ws_bytes < 0:
-        raise _ffi.HipBackendError(f"spamd_attention_ws_bytes failed: {ws_bytes}")
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
-    has_scale = scale is not None
-    sc = float(np.asarray(scale).astype(np_dtype(dt))) if has_scale else 0.0
+    ws, ws_bytes = _seg_workspace("spamd_attention_ws_bytes", dev, code_of(dt), nnz, H, Dv, chunk) if max_len > chunk else (None, 0)
+    b2, bh = (None, 0)
+    if bias is not None:
+        require_hip(indptr, bias)
+        b2, bh = _bias2(bias, lead, H, nnz, dt, "attention")      # (nnz == 0: no pointer, which the entry takes for no bias - rightly)
+    # one argument list; the entry - plain, with a bias, with dropout - takes what it knows of the middle
     if dz is not None:
-        b2, bh = (None, 0) if bias is None else _bias2(bias, lead, H, nnz, dt, "attention")
-        if bias is not None:
-            require_hip(indptr, bias)
-        _ffi.call("spamd_attention_dropout", code_of(dt), code_of(indptr.dtype), M, N, nnz, H, D, Dv, ptr(indptr.contiguous()),
-                  ptr(indices.contiguous()), ptr(svals.contiguous()), ptr(q3), qp, qh, ptr(k3), kp, kh, ptr(v3), vp, vh,
-                  int(has_scale), sc, group, short_max, chunk, max_len, ptr(b2), bh, dz[0], dz[1], 0, ptr(ws), ws_bytes, ptr(out),
-                  stream_ptr(dev))
-        return out
-    if bias is None:
-        _ffi.call("spamd_attention", code_of(dt), code_of(indptr.dtype), M, N, nnz, H, D, Dv, ptr(indptr.contiguous()),
-                  ptr(indices.contiguous()), ptr(svals.contiguous()), ptr(q3), qp, qh, ptr(k3), kp, kh, ptr(v3), vp, vh,
-                  int(has_scale), sc, group, short_max, chunk, max_len, ptr(ws), ws_bytes, ptr(out), stream_ptr(dev))
-        return out
-    require_hip(indptr, bias)
-    b2, bh = _bias2(bias, lead, H, nnz, dt, "attention")      # (nnz == 0: no pointer, which the entry takes for no bias - rightly)
-    _ffi.call("spamd_attention_bias", code_of(dt), code_of(indptr.dtype), M, N, nnz, H, D, Dv, ptr(indptr.contiguous()),
-              ptr(indices.contiguous()), ptr(svals.contiguous()), ptr(q3), qp, qh, ptr(k3), kp, kh, ptr(v3), vp, vh,
-              int(has_scale), sc, group, short_max, chunk, max_len, ptr(b2), bh, ptr(ws), ws_bytes, ptr(out), stream_ptr(dev))
+        entry, mods = "spamd_attention_dropout", (ptr(b2), bh, dz[0], dz[1], 0)
+    elif bias is not None:
+        entry, mods = "spamd_attention_bias", (ptr(b2), bh)
+    else:
+        entry, mods = "spamd_attention", ()
+    _ffi.call(entry, code_of(dt), code_of(indptr.dtype), M, N, nnz, H, D, Dv, ptr(indptr.contiguous()), ptr(indices.contiguous()),
+              ptr(svals.contiguous()), ptr(q3), qp, qh, ptr(k3), kp, kh, ptr(v3), vp, vh, *_seg_scale(scale, dt), group, short_max, chunk,
+              max_len, *mods, ptr(ws), ws_bytes, ptr(out), stream_ptr(dev))
     return out
 
 
@@ -1920,11 +1922,8 @@ def attention_grad_rows(indptr, indices, svals, colptr, colperm, colrows, q, k, 
         raise ValueError("attention_grad: shape mismatch between the mask, the column grouping, q, k, v and g")
     if form not in (None,) + ATTENTION_FORMS:
         raise ValueError(f"attention_grad: form must be one of {ATTENTION_FORMS} or None, got {form!r}")
-    chunk = (64 if form == "long" else attention_grad_chunk()) if chunk is None else int(chunk)
-    short_max = (ATTENTION_GRAD_SHORT_MAX if short_max is None else int(short_max)) if form in (None, "short") else 0
-    longest = max(max_row, max_col)
-    if form == "short" and longest > 64 or form == "wide" and longest > chunk:
-        raise ValueError(f"attention_grad: form {form!r} does not take a row or column of {longest} elements")
+    chunk, short_max = _seg_forms("attention_grad", form, chunk, short_max, max(max_row, max_col), attention_grad_chunk(),
+                                  ATTENTION_GRAD_SHORT_MAX, "row or column")
     group = ATTENTION_GRAD_GROUP if group is None else int(group)
     col_group = ATTENTION_GRAD_COL_GROUP if col_group is None else int(col_group)
     q3, qp, qh = _rows3(q, dev)
@@ -1935,41 +1934,26 @@ def attention_grad_rows(indptr, indices, svals, colptr, colperm, colrows, q, k, 
     dq = torch.empty(lead + (M, D), dtype=dt, device=dev)
     dk = torch.empty(lead + (N, D), dtype=dt, device=dev)
     dv = torch.empty(lead + (N, Dv), dtype=dt, device=dev)
-    ws_bytes = int(_ffi.lib().spamd_attention_grad_ws_bytes(code_of(dt), nnz, H, D, Dv, chunk))
-    if ws_bytes < 0:
-        raise _ffi.HipBackendError(f"spamd_attention_grad_ws_bytes failed: {ws_bytes}")
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
-    has_scale = scale is not None
-    sc = float(np.asarray(scale).astype(np_dtype(dt))) if has_scale else 0.0
-    if dz is not None:
-        b2, bh = (None, 0) if bias is None else _bias2(bias, lead, H, nnz, dt, "attention_grad")
-        if bias is not None:
-            require_hip(indptr, bias)
-        dbias = None
-        if bias is not None and want_dbias:
+    ws, ws_bytes = _seg_workspace("spamd_attention_grad_ws_bytes", dev, code_of(dt), nnz, H, D, Dv, chunk)
+    b2, bh, dbias = None, 0, None
+    if bias is not None:
+        require_hip(indptr, bias)
+        b2, bh = _bias2(bias, lead, H, nnz, dt, "attention_grad")
+        # every element is written by the row pass, which the entry skips only when dq, dk and dv are all empty (D = Dv = 0: z = 0)
+        if want_dbias:
             dbias = (torch.zeros if D == 0 and Dv == 0 else torch.empty)(lead + (nnz,), dtype=dt, device=dev)
-        _ffi.call("spamd_attention_grad_dropout", code_of(dt), code_of(indptr.dtype), M, N, nnz, H, D, Dv, ptr(indptr.contiguous()),
-                  ptr(indices.contiguous()), ptr(svals.contiguous()), ptr(colptr.contiguous()), ptr(colperm.contiguous()),
-                  ptr(colrows.contiguous()), ptr(q3), qp, qh, ptr(k3), kp, kh, ptr(v3), vp, vh, ptr(g3), gp, gh, int(has_scale), sc,
-                  group, col_group, short_max, chunk, max_row, max_col, ptr(b2), bh, ptr(dbias), dz[0], dz[1], 0, ptr(ws), ws_bytes,
-                  ptr(dq), ptr(dk), ptr(dv), stream_ptr(dev))
-        return (dq, dk, dv) if bias is None else (dq, dk, dv, dbias)
-    if bias is None:
-        _ffi.call("spamd_attention_grad", code_of(dt), code_of(indptr.dtype), M, N, nnz, H, D, Dv, ptr(indptr.contiguous()),
-                  ptr(indices.contiguous()), ptr(svals.contiguous()), ptr(colptr.contiguous()), ptr(colperm.contiguous()),
-                  ptr(colrows.contiguous()), ptr(q3), qp, qh, ptr(k3), kp, kh, ptr(v3), vp, vh, ptr(g3), gp, gh, int(has_scale), sc,
-                  group, col_group, short_max, chunk, max_row, max_col, ptr(ws), ws_bytes, ptr(dq), ptr(dk), ptr(dv), stream_ptr(dev))
-        return dq, dk, dv
-    require_hip(indptr, bias)
-    b2, bh = _bias2(bias, lead, H, nnz, dt, "attention_grad")
-    # every element is written by the row pass, which the entry skips only when dq, dk and dv are all empty (D = Dv = 0: z = 0)
-    dbias = (torch.zeros if D == 0 and Dv == 0 else torch.empty)(lead + (nnz,), dtype=dt, device=dev) if want_dbias else None
-    _ffi.call("spamd_attention_grad_bias", code_of(dt), code_of(indptr.dtype), M, N, nnz, H, D, Dv, ptr(indptr.contiguous()),
-              ptr(indices.contiguous()), ptr(svals.contiguous()), ptr(colptr.contiguous()), ptr(colperm.contiguous()),
-              ptr(colrows.contiguous()), ptr(q3), qp, qh, ptr(k3), kp, kh, ptr(v3), vp, vh, ptr(g3), gp, gh, int(has_scale), sc,
-              group, col_group, short_max, chunk, max_row, max_col, ptr(b2), bh, ptr(dbias), ptr(ws), ws_bytes, ptr(dq), ptr(dk),
-              ptr(dv), stream_ptr(dev))
-    return dq, dk, dv, dbias
+    # one argument list; the entry - plain, with a bias, with dropout - takes what it knows of the middle
+    if dz is not None:
+        entry, mods = "spamd_attention_grad_dropout", (ptr(b2), bh, ptr(dbias), dz[0], dz[1], 0)
+    elif bias is not None:
+        entry, mods = "spamd_attention_grad_bias", (ptr(b2), bh, ptr(dbias))
+    else:
+        entry, mods = "spamd_attention_grad", ()
+    _ffi.call(entry, code_of(dt), code_of(indptr.dtype), M, N, nnz, H, D, Dv, ptr(indptr.contiguous()), ptr(indices.contiguous()),
+              ptr(svals.contiguous()), ptr(colptr.contiguous()), ptr(colperm.contiguous()), ptr(colrows.contiguous()), ptr(q3), qp, qh,
+              ptr(k3), kp, kh, ptr(v3), vp, vh, ptr(g3), gp, gh, *_seg_scale(scale, dt), group, col_group, short_max, chunk, max_row,
+              max_col, *mods, ptr(ws), ws_bytes, ptr(dq), ptr(dk), ptr(dv), stream_ptr(dev))
+    return (dq, dk, dv) if bias is None else (dq, dk, dv, dbias)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -2068,10 +2052,7 @@ def semiring_spmm(indptr, indices, vals, b, max_len, *, add, mul, init=None, ret
     i2, ldi = (None, N) if init is None else _pitched2(init if b.ndim == 2 else init.unsqueeze(1))
     out = torch.empty((M, N), dtype=dt, device=dev)
     arg = torch.empty((M, N), dtype=torch.int64, device=dev) if return_arg else None
-    ws_bytes = int(_ffi.lib().spamd_semiring_spmm_ws_bytes(code_of(dt), nnz, N, chunk, int(return_arg))) if max_len > chunk else 0
-    if ws_bytes < 0:
-        raise _ffi.HipBackendError(f"spamd_semiring_spmm_ws_bytes failed: {ws_bytes}")
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    ws, ws_bytes = _seg_workspace("spamd_semiring_spmm_ws_bytes", dev, code_of(dt), nnz, N, chunk, int(return_arg)) if max_len > chunk else (None, 0)
     _ffi.call("spamd_semiring_spmm", code_of(dt), code_of(indptr.dtype), SEMIRING_ADDS.index(add), SEMIRING_MULS.index(mul), M, K, N,
               nnz, ptr(indptr.contiguous()), ptr(indices.contiguous()), ptr(vals.contiguous()), ptr(b2), ldb, ptr(i2), ldi,
               int(narrow), group, chunk, max_len, ptr(ws), ws_bytes, ptr(out), N, ptr(arg), N, stream_ptr(dev))
@@ -2166,10 +2147,8 @@ def semiring_grad(indptr, indices, vals, colptr, colperm, colrows, b, arg, g, ma
     if want_db and (int(colptr.numel()) != K + 1 or int(colperm.numel()) != nnz or int(colrows.numel()) != nnz):
         raise ValueError("semiring_grad: shape mismatch between the column grouping, the CSR arrays and b")
     max_col = int(max_col or 0)
-    chunk = (64 if col_form == "long" else SEMIRING_GRAD_CHUNK) if chunk is None else int(chunk)
-    short_max = (SEMIRING_GRAD_SHORT_MAX if short_max is None else int(short_max)) if col_form in (None, "short") else 0
-    if want_db and (col_form == "short" and max_col > 64 or col_form == "wide" and max_col > chunk):
-        raise ValueError(f"semiring_grad: col_form {col_form!r} does not take a column of {max_col} elements")
+    chunk, short_max = _seg_forms("semiring_grad", col_form, chunk, short_max, max_col if want_db else 0, SEMIRING_GRAD_CHUNK,
+                                  SEMIRING_GRAD_SHORT_MAX, "column", name="col_form")
     if col_group is None:
         col_group = _semiring_grad_col_group(N, b.element_size())
     elif col_group == 1 and N > SEMIRING_GRAD_LANE_MAX_N:
@@ -2191,10 +2170,7 @@ def semiring_grad(indptr, indices, vals, colptr, colperm, colrows, b, arg, g, ma
     da = torch.empty(nnz, dtype=dt, device=dev) if want_da else None
     db = torch.empty((K, N), dtype=dt, device=dev) if want_db else None
     di = torch.empty((M, N), dtype=dt, device=dev) if want_di else None
-    ws_bytes = int(_ffi.lib().spamd_semiring_grad_ws_bytes(code_of(dt), nnz, N, chunk)) if want_db and max_col > chunk else 0
-    if ws_bytes < 0:
-        raise _ffi.HipBackendError(f"spamd_semiring_grad_ws_bytes failed: {ws_bytes}")
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    ws, ws_bytes = _seg_workspace("spamd_semiring_grad_ws_bytes", dev, code_of(dt), nnz, N, chunk) if want_db and max_col > chunk else (None, 0)
     cp, cm, cr = (colptr.contiguous(), colperm.contiguous(), colrows.contiguous()) if want_db else (None, None, None)
     SEMIRING_GRAD_STATS.update(da=want_da, db=want_db, dinit=want_di)
     _ffi.call("spamd_semiring_grad", code_of(dt), code_of(indptr.dtype), SEMIRING_MULS.index(mul), M, K, N, nnz, ptr(indptr.contiguous()),

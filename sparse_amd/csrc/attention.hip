@@ -23,7 +23,7 @@
 //          short form finds it; then the lanes run along Dv, p_i and c_i broadcast by shuffle, four v rows in flight.
 //   wide   short_max < n <= chunk: a wave (a workgroup of its own) per (row, head); the scores are parked in LDS (chunk values),
 //          A14's wide form runs over them in place, then the same output loop.
-//   long   n > chunk: unfused through the workspace, in pieces of `chunk` elements found by windows as in csrc/softmax.hip.
+//   long   n > chunk: unfused through the workspace, in pieces of `chunk` elements found by windows (csrc/segment_walk.h).
 //          Six launches that each END before the next reads what it wrote: piece scores and maxima, row maxima, piece sums,
 //          row sums (piece order), piece outputs, row outputs (piece order).
 #include "attention_common.h"
@@ -175,19 +175,10 @@ at_wide_kernel(AtIn<T, I> in, int64_t above, int64_t upto, AtMods<T, B, P> mz) {
     const int64_t head = blockIdx.y;
     const T* __restrict__ kh = in.k + head * in.kh;
     const T* __restrict__ vh = in.v + head * in.vh;
-    for (int64_t base = (int64_t)blockIdx.x * 64; base < in.M; base += (int64_t)gridDim.x * 64) {
-      const int64_t mine = base + lane;
-      int64_t mb = 0, mn = 0;
-      if (mine < in.M) {
-        mb = (int64_t)in.ptr[mine];
-        mn = (int64_t)in.ptr[mine + 1] - mb;
-      }
-      unsigned long long todo = __ballot(mn > above && mn <= upto);
-      while (todo) {   // wave-uniform: all 64 lanes stay together
-        const int src = __builtin_ctzll(todo);
-        todo &= todo - 1;
-        const int64_t row = base + src, b = wave_bcast(mb, src);
-        const int n = (int)wave_bcast(mn, src);
+    for (int64_t base = (int64_t)blockIdx.x * 64; base < in.M; base += (int64_t)gridDim.x * 64)
+      seg_wave_each(in.ptr, in.M, base, lane, [&](int64_t len) { return len > above && len <= upto; }, [&](int src, int64_t b, int64_t len) {
+        const int64_t row = base + src;
+        const int n = (int)len;
         const T* __restrict__ qrow = in.q + head * in.qh + row * in.qp;
         const I* __restrict__ idx = in.idx + b;
         for (int i = 0; i < n; i += 4) {
@@ -224,8 +215,7 @@ at_wide_kernel(AtIn<T, I> in, int64_t above, int64_t upto, AtMods<T, B, P> mz) {
           if (j < in.Dv) orow[j] = o;
         }
         __syncthreads();   // the next row writes the scores again
-      }
-    }
+      });
   }
 }
 
@@ -243,7 +233,7 @@ __device__ __forceinline__ void at_piece(const AtIn<T, I>& in, const AtBias<T, B
   T* __restrict__ sc = ws;
   T* __restrict__ st = ws + nnz;
   T* __restrict__ part = ws + nnz + 8 * nwin;
-  const int64_t slot = at_slot(b, s, chunk), slot0 = at_slot(b, b, chunk);
+  const int64_t slot = seg_slot(b, s, chunk), slot0 = seg_slot(b, b, chunk);
   if (PHASE == 0) {
     const T* __restrict__ kh = in.k + head * in.kh;
     const T* __restrict__ qrow = in.q + head * in.qh + row * in.qp;
@@ -314,24 +304,10 @@ at_piece_kernel(AtIn<T, I> in, int64_t nnz, int64_t chunk, int64_t nwin, T* __re
   {
     const int64_t head = blockIdx.y;
     T* __restrict__ ws = ws_all + head * at_ws_values(nnz, nwin, in.Dv);
-    for (int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); g < nwin; g += (int64_t)gridDim.x * 4) {
-      const int64_t lo = g * chunk;
-      const int64_t hi = lo + chunk < nnz ? lo + chunk : nnz;
-      const int64_t r0 = at_row_of(in.ptr, M, lo);   // lo < nnz: r0 < M and the row is not empty
-      {
-        const int64_t b0 = (int64_t)in.ptr[r0], e0 = (int64_t)in.ptr[r0 + 1];
-        if (e0 - b0 > chunk) {
-          const int64_t s = b0 + (lo - b0 + chunk - 1) / chunk * chunk;   // the one piece start of this row in [lo, lo + chunk)
-          if (s < hi && s < e0)
-            at_piece<T, I, PHASE, B, P>(in, bz, dz, head, r0, b0, s, s + chunk < e0 ? s + chunk : e0, chunk, nnz, nwin, lane, ws);
-        }
-      }
-      const int64_t r1 = at_row_of(in.ptr, M, hi - 1);
-      if (r1 > r0) {   // starts inside the window; only the last such row can be longer than the window
-        const int64_t b1 = (int64_t)in.ptr[r1], e1 = (int64_t)in.ptr[r1 + 1];
-        if (e1 - b1 > chunk) at_piece<T, I, PHASE, B, P>(in, bz, dz, head, r1, b1, b1, b1 + chunk, chunk, nnz, nwin, lane, ws);
-      }
-    }
+    for (int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); g < nwin; g += (int64_t)gridDim.x * 4)
+      seg_window_pieces(in.ptr, M, nnz, chunk, g, [&](int64_t row, int64_t b, int64_t s, int64_t e) {
+        at_piece<T, I, PHASE, B, P>(in, bz, dz, head, row, b, s, e, chunk, nnz, nwin, lane, ws);
+      });
   }
 }
 
@@ -347,90 +323,48 @@ at_join_kernel(AtIn<T, I> in, int64_t nnz, int64_t chunk, int64_t nwin, T* __res
     const int64_t head = blockIdx.y;
     T* __restrict__ st = ws_all + head * at_ws_values(nnz, nwin, in.Dv) + nnz;
     const T* __restrict__ part = st + 8 * nwin;
-    for (int64_t base = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64; base < in.M; base += nwaves * 64) {
-      const int64_t mine = base + lane;
-      int64_t mb = 0, mn = 0;
-      if (mine < in.M) {
-        mb = (int64_t)in.ptr[mine];
-        mn = (int64_t)in.ptr[mine + 1] - mb;
-      }
-      unsigned long long todo = __ballot(mn > chunk);
-      while (todo) {
-        const int src = __builtin_ctzll(todo);
-        todo &= todo - 1;
-        const int64_t b = wave_bcast(mb, src), n = wave_bcast(mn, src);
+    for (int64_t base = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64; base < in.M; base += nwaves * 64)
+      seg_wave_each(in.ptr, in.M, base, lane, [&](int64_t len) { return len > chunk; }, [&](int src, int64_t b, int64_t n) {
         const int64_t np = (n + chunk - 1) / chunk;
-        const int64_t slot0 = at_slot(b, b, chunk);
+        const int64_t slot0 = seg_slot(b, b, chunk);
         if (PHASE == 0) {
           T m = at_neg_inf<T>();
-          for (int64_t k = lane; k < np; k += 64) m = at_nmax(m, st[at_slot(b, b + k * chunk, chunk)]);
+          for (int64_t k = lane; k < np; k += 64) m = at_nmax(m, st[seg_slot(b, b + k * chunk, chunk)]);
           m = at_xmax<T, 64>(m);
           if (lane == 0) st[4 * nwin + slot0] = m;
         } else if (PHASE == 1) {
-          T s = T(0);
-          for (int64_t k0 = 0; k0 < np; k0 += 64) {
-            const int cnt = (int)(np - k0 < 64 ? np - k0 : 64);
-            const T v = lane < cnt ? st[2 * nwin + at_slot(b, b + (k0 + lane) * chunk, chunk)] : T(0);
-            for (int u = 0; u < cnt; ++u) {
-              const T pv = wave_bcast(v, u);
-              s = (k0 + u == 0) ? pv : s + pv;
-            }
-          }
+          const T s = seg_join_sum<T>(np, lane, [&](int64_t k) { return st[2 * nwin + seg_slot(b, b + k * chunk, chunk)]; });
           if (lane == 0) st[6 * nwin + slot0] = s;
         } else {
           T* __restrict__ orow = in.out + (head * in.M + base + src) * in.Dv;
-          for (int j = lane; j < in.Dv; j += 64) {
-            T s = part[slot0 * (int64_t)in.Dv + j];
-            for (int64_t k = 1; k < np; ++k) s = s + part[at_slot(b, b + k * chunk, chunk) * (int64_t)in.Dv + j];
-            orow[j] = s;
-          }
+          seg_join_rows(part, in.Dv, in.Dv, b, np, chunk, lane, [&](int64_t j, T s) { orow[j] = s; });
         }
-      }
-    }
+      });
   }
-}
-
-static unsigned at_grid(int64_t items, int64_t per_block) {
-  return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(items, per_block), (int64_t)1 << 20));
 }
 
 template <typename T, typename I, bool B, bool P>
 static int attention_typed(AtIn<T, I> in, AtBias<T, B> bz, AtDrop<T, P> dz, int64_t nnz, int group, int64_t short_max, int64_t chunk,
                            int64_t max_len, void* ws_, hipStream_t st) {
   const unsigned gy = (unsigned)in.H;
-  {   // (always: the rows without a stored element are written here)
-#define AT_SHORT(G) \
-  hipLaunchKernelGGL((at_short_kernel<T, I, G, B, P>), dim3(at_grid(in.M, 256 / G), gy), dim3(256), 0, st, in, short_max, AtMods<T, B, P>(bz, dz))
-    if (group == 8) AT_SHORT(8);
-    else if (group == 16) AT_SHORT(16);
-    else if (group == 32) AT_SHORT(32);
-    else AT_SHORT(64);
-#undef AT_SHORT
-    if (int rc = launch_status()) return rc;
-  }
-  if (std::min(max_len, chunk) > short_max) {
-    hipLaunchKernelGGL((at_wide_kernel<T, I, B, P>), dim3(at_grid(in.M, 64), gy), dim3(64), (size_t)chunk * sizeof(T), st, in, short_max,
-                       chunk, AtMods<T, B, P>(bz, dz));
-    if (int rc = launch_status()) return rc;
-  }
+  const dim3 wg(256);
+  // (always: the rows without a stored element are written here)
+  SEG_GROUP(group, G, SPAMD_LAUNCH((at_short_kernel<T, I, G, B, P>), dim3(seg_grid(in.M, 256 / G), gy), wg, 0, st, in, short_max, AtMods<T, B, P>(bz, dz)));
+  if (std::min(max_len, chunk) > short_max)
+    SPAMD_LAUNCH((at_wide_kernel<T, I, B, P>), dim3(seg_grid(in.M, 64), gy), dim3(64), (size_t)chunk * sizeof(T), st, in, short_max, chunk,
+                 AtMods<T, B, P>(bz, dz));
   if (max_len > chunk) {
     T* ws = (T*)ws_;
     const int64_t nwin = ceil_div(nnz, chunk);
-    const dim3 pg(at_grid(nwin, 4), gy), jg(at_grid(in.M, 256), gy);
+    const dim3 pg(seg_grid(nwin, 4), gy), jg(seg_grid(in.M, 256), gy);
     const AtBias<T, false> nob{};   // the biased scores are in the workspace from here on
     const AtDrop<T, false> nod{};   // only the piece outputs see dropout
-    hipLaunchKernelGGL((at_piece_kernel<T, I, 0, B, false>), pg, dim3(256), 0, st, in, nnz, chunk, nwin, ws, AtMods<T, B, false>(bz, nod));
-    if (int rc = launch_status()) return rc;
-    hipLaunchKernelGGL((at_join_kernel<T, I, 0>), jg, dim3(256), 0, st, in, nnz, chunk, nwin, ws);
-    if (int rc = launch_status()) return rc;
-    hipLaunchKernelGGL((at_piece_kernel<T, I, 1, false, false>), pg, dim3(256), 0, st, in, nnz, chunk, nwin, ws, AtMods<T, false, false>(nob, nod));
-    if (int rc = launch_status()) return rc;
-    hipLaunchKernelGGL((at_join_kernel<T, I, 1>), jg, dim3(256), 0, st, in, nnz, chunk, nwin, ws);
-    if (int rc = launch_status()) return rc;
-    hipLaunchKernelGGL((at_piece_kernel<T, I, 2, false, P>), pg, dim3(256), 0, st, in, nnz, chunk, nwin, ws, AtMods<T, false, P>(nob, dz));
-    if (int rc = launch_status()) return rc;
-    hipLaunchKernelGGL((at_join_kernel<T, I, 2>), jg, dim3(256), 0, st, in, nnz, chunk, nwin, ws);
-    if (int rc = launch_status()) return rc;
+    SPAMD_LAUNCH((at_piece_kernel<T, I, 0, B, false>), pg, wg, 0, st, in, nnz, chunk, nwin, ws, AtMods<T, B, false>(bz, nod));
+    SPAMD_LAUNCH((at_join_kernel<T, I, 0>), jg, wg, 0, st, in, nnz, chunk, nwin, ws);
+    SPAMD_LAUNCH((at_piece_kernel<T, I, 1, false, false>), pg, wg, 0, st, in, nnz, chunk, nwin, ws, AtMods<T, false, false>(nob, nod));
+    SPAMD_LAUNCH((at_join_kernel<T, I, 1>), jg, wg, 0, st, in, nnz, chunk, nwin, ws);
+    SPAMD_LAUNCH((at_piece_kernel<T, I, 2, false, P>), pg, wg, 0, st, in, nnz, chunk, nwin, ws, AtMods<T, false, P>(nob, dz));
+    SPAMD_LAUNCH((at_join_kernel<T, I, 2>), jg, wg, 0, st, in, nnz, chunk, nwin, ws);
   }
   return 0;
 }
@@ -492,7 +426,7 @@ using namespace spamd;
 extern "C" int64_t spamd_attention_ws_bytes(int val_dtype, int64_t nnz, int64_t H, int64_t Dv, int64_t chunk) {
   const int64_t esz = val_dtype == SPAMD_F32 ? 4 : (val_dtype == SPAMD_F64 ? 8 : 0);
   if (!esz) return SPAMD_ETYPE;
-  if (nnz < 0 || H < 0 || Dv < 0 || chunk < 64 || chunk > ATTENTION_MAX_CHUNK || chunk % 64) return SPAMD_EINVAL;
+  if (nnz < 0 || H < 0 || Dv < 0 || !seg_chunk_ok(chunk, ATTENTION_MAX_CHUNK)) return SPAMD_EINVAL;
   if (nnz <= chunk) return 0;
   return H * at_ws_values(nnz, ceil_div(nnz, chunk), Dv) * esz;
 }
@@ -513,8 +447,7 @@ extern "C" int spamd_attention_dropout(int val_dtype, int idx_dtype, int64_t M, 
   if (q_pitch < 0 || q_head < 0 || k_pitch < 0 || k_head < 0 || v_pitch < 0 || v_head < 0) return SPAMD_EINVAL;
   if (bias_head < 0) return SPAMD_EINVAL;
   if (!dropout_rate_ok(rate) || head0 < 0) return SPAMD_EINVAL;
-  if (group != 8 && group != 16 && group != 32 && group != 64) return SPAMD_EINVAL;
-  if (chunk < 64 || chunk > ATTENTION_MAX_CHUNK || chunk % 64 || short_max < 0 || short_max > 64) return SPAMD_EINVAL;
+  if (!seg_params_ok(group, chunk, ATTENTION_MAX_CHUNK, short_max)) return SPAMD_EINVAL;
   if (M == 0 || H == 0 || Dv == 0) return 0;
   if (!out || !s_ptr) return SPAMD_EINVAL;
   if (nnz > 0 && (!s_idx || !s_val || !k || !v || (D > 0 && !q))) return SPAMD_EINVAL;
@@ -560,7 +493,7 @@ extern "C" int spamd_attention_keep(int64_t nnz, int64_t H, int64_t pos0, int64_
   if (nnz == 0 || H == 0) return 0;
   if (H > INT64_MAX / nnz || !out) return SPAMD_EINVAL;
   const int64_t total = nnz * H;
-  hipLaunchKernelGGL(at_keep_kernel, dim3(at_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, nnz, total, (uint64_t)pos0,
-                     (uint64_t)head0, (uint64_t)seed, dropout_threshold(rate), out);
-  return launch_status();
+  SPAMD_LAUNCH(at_keep_kernel, dim3(seg_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, nnz, total, (uint64_t)pos0, (uint64_t)head0,
+               (uint64_t)seed, dropout_threshold(rate), out);
+  return 0;
 }

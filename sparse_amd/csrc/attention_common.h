@@ -1,8 +1,9 @@
 // Device helpers shared by csrc/attention.hip (A15) and csrc/attention_grad.hip (A16): the NaN-propagating maximum, the
-// halving folds, the 64-accumulator dot product of four gathered rows, the four-rows-in-flight fma loops and the window
-// arithmetic of the piece forms.  Moved here unchanged, so that both files compute the same bits from the same code.
+// halving folds, the 64-accumulator dot product of four gathered rows and the four-rows-in-flight fma loops, so that both files
+// compute the same bits from the same code.  csrc/softmax.hip (A14) and the semiring products (A17, A18) use the maximum and the
+// folds too.  The segment walk of the piece forms is csrc/segments.h.
 #pragma once
-#include "common.h"
+#include "segments.h"
 
 #include <algorithm>
 #include <limits>
@@ -169,24 +170,6 @@ __device__ __forceinline__ T at_wave_out(const T* __restrict__ vh, int64_t vp, i
       if (i + e < cnt) acc = at_fma(pp[e], vv[e], acc);
   }
   return acc;
-}
-
-// last r in [0, M] with ptr[r] <= pos (ptr[0] = 0 <= pos): the non-empty row that holds pos when pos < nnz
-template <typename I>
-__device__ __forceinline__ int64_t at_row_of(const I* __restrict__ ptr, int64_t M, int64_t pos) {
-  int64_t lo = 0, hi = M;
-  while (lo < hi) {
-    const int64_t mid = lo + (hi - lo + 1) / 2;
-    if ((int64_t)ptr[mid] <= pos) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
-// the workspace slot of the piece of a long row (first position b) that starts at position s: window g = s / chunk holds at
-// most two piece starts of long rows (csrc/mttkrp.hip has the argument) - slots 2g and 2g + 1
-__device__ __forceinline__ int64_t at_slot(int64_t b, int64_t s, int64_t chunk) {
-  return 2 * (s / chunk) + (s == b && b % chunk != 0 ? 1 : 0);
 }
 
 }  // namespace spamd

@@ -267,6 +267,7 @@ ag_wide_kernel(AgIn<T, I> in, int64_t above, int64_t upto, AtMods<T, B, P> mz) {
   const T* __restrict__ vh = in.v + head * in.vh;
   T* __restrict__ wp = in.ws + head * in.ws_head;
   T* __restrict__ wy = wp + in.nnz;
+  // (the ballot loop of seg_wave_each, written out: through the helper the bias-and-dropout instances spill one scalar more)
   for (int64_t base = (int64_t)blockIdx.x * 64; base < in.M; base += (int64_t)gridDim.x * 64) {
     const int64_t mine = base + lane;
     int64_t mb = 0, mn = 0;
@@ -374,7 +375,7 @@ __device__ __forceinline__ void ag_piece(const AgIn<T, I>& in, const AtBias<T, B
   T* __restrict__ st = ws + 2 * in.nnz;
   const int64_t W = (int64_t)in.D + in.Dv;
   T* __restrict__ part = st + 12 * nwin;
-  const int64_t slot = at_slot(b, s, chunk), slot0 = at_slot(b, b, chunk);
+  const int64_t slot = seg_slot(b, s, chunk), slot0 = seg_slot(b, b, chunk);
   if (PHASE == 0) {
     const T* __restrict__ kh = in.k + head * in.kh;
     const T* __restrict__ vh = in.v + head * in.vh;
@@ -457,7 +458,7 @@ __device__ __forceinline__ void ag_piece(const AgIn<T, I>& in, const AtBias<T, B
   }
 }
 
-// a wave per window of `chunk` positions: the window holds at most two piece starts of long rows (csrc/attention.hip)
+// a wave per window of `chunk` positions: the window holds at most two piece starts of long rows (csrc/segment_walk.h)
 // (P: the phases that see dropout are 2 - ed_i - and 3 - pd_i)
 template <typename T, typename I, int PHASE, bool B, bool P>
 __global__ void __launch_bounds__(256)
@@ -469,23 +470,10 @@ ag_piece_kernel(AgIn<T, I> in, int64_t chunk, int64_t nwin, AtMods<T, B, P> mz) 
   const int64_t R = PHASE == 5 ? in.N : in.M, nnz = in.nnz;
   const int64_t head = blockIdx.y;
   T* __restrict__ ws = in.ws + head * in.ws_head;
-  for (int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); g < nwin; g += (int64_t)gridDim.x * 4) {
-    const int64_t lo = g * chunk;
-    const int64_t hi = lo + chunk < nnz ? lo + chunk : nnz;
-    const int64_t r0 = at_row_of(ptr, R, lo);   // lo < nnz: r0 < R and the row is not empty
-    {
-      const int64_t b0 = (int64_t)ptr[r0], e0 = (int64_t)ptr[r0 + 1];
-      if (e0 - b0 > chunk) {
-        const int64_t s = b0 + (lo - b0 + chunk - 1) / chunk * chunk;   // the one piece start of this row in [lo, lo + chunk)
-        if (s < hi && s < e0) ag_piece<T, I, PHASE, B, P>(in, bz, dz, head, r0, b0, s, s + chunk < e0 ? s + chunk : e0, chunk, nwin, lane, ws);
-      }
-    }
-    const int64_t r1 = at_row_of(ptr, R, hi - 1);
-    if (r1 > r0) {   // starts inside the window; only the last such row can be longer than the window
-      const int64_t b1 = (int64_t)ptr[r1], e1 = (int64_t)ptr[r1 + 1];
-      if (e1 - b1 > chunk) ag_piece<T, I, PHASE, B, P>(in, bz, dz, head, r1, b1, b1, b1 + chunk, chunk, nwin, lane, ws);
-    }
-  }
+  for (int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); g < nwin; g += (int64_t)gridDim.x * 4)
+    seg_window_pieces(ptr, R, nnz, chunk, g, [&](int64_t row, int64_t b, int64_t s, int64_t e) {
+      ag_piece<T, I, PHASE, B, P>(in, bz, dz, head, row, b, s, e, chunk, nwin, lane, ws);
+    });
 }
 
 // row phases: 0 row maxima; 1 row sums, 2 row deltas (piece values added one after the other in piece order); 3 dq rows.
@@ -502,56 +490,31 @@ ag_join_kernel(AgIn<T, I> in, int64_t chunk, int64_t nwin) {
   const int64_t head = blockIdx.y;
   T* __restrict__ st = in.ws + head * in.ws_head + 2 * in.nnz;
   const T* __restrict__ part = st + 12 * nwin;
-  for (int64_t base = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64; base < R; base += nwaves * 64) {
-    const int64_t mine = base + lane;
-    int64_t mb = 0, mn = 0;
-    if (mine < R) {
-      mb = (int64_t)ptr[mine];
-      mn = (int64_t)ptr[mine + 1] - mb;
-    }
-    unsigned long long todo = __ballot(mn > chunk);
-    while (todo) {
-      const int src = __builtin_ctzll(todo);
-      todo &= todo - 1;
-      const int64_t b = wave_bcast(mb, src), n = wave_bcast(mn, src);
+  for (int64_t base = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64; base < R; base += nwaves * 64)
+    seg_wave_each(ptr, R, base, lane, [&](int64_t len) { return len > chunk; }, [&](int src, int64_t b, int64_t n) {
       const int64_t np = (n + chunk - 1) / chunk;
-      const int64_t slot0 = at_slot(b, b, chunk);
+      const int64_t slot0 = seg_slot(b, b, chunk);
       if (PHASE == 0) {
         T m = at_neg_inf<T>();
-        for (int64_t k = lane; k < np; k += 64) m = at_nmax(m, st[at_slot(b, b + k * chunk, chunk)]);
+        for (int64_t k = lane; k < np; k += 64) m = at_nmax(m, st[seg_slot(b, b + k * chunk, chunk)]);
         m = at_xmax<T, 64>(m);
         if (lane == 0) st[4 * nwin + slot0] = m;
       } else if (PHASE == 1 || PHASE == 2) {
         const int64_t from = PHASE == 1 ? 2 * nwin : 8 * nwin, to = PHASE == 1 ? 6 * nwin : 10 * nwin;
-        T s = T(0);
-        for (int64_t k0 = 0; k0 < np; k0 += 64) {
-          const int cnt = (int)(np - k0 < 64 ? np - k0 : 64);
-          const T v = lane < cnt ? st[from + at_slot(b, b + (k0 + lane) * chunk, chunk)] : T(0);
-          for (int u = 0; u < cnt; ++u) {
-            const T pv = wave_bcast(v, u);
-            s = (k0 + u == 0) ? pv : s + pv;
-          }
-        }
+        const T s = seg_join_sum<T>(np, lane, [&](int64_t k) { return st[from + seg_slot(b, b + k * chunk, chunk)]; });
         if (lane == 0) st[to + slot0] = s;
       } else if (PHASE == 3) {
         T* __restrict__ orow = in.dq + (head * in.M + base + src) * in.D;
-        for (int j = lane; j < in.D; j += 64) {
-          T s = part[slot0 * W + j];
-          for (int64_t k = 1; k < np; ++k) s = s + part[at_slot(b, b + k * chunk, chunk) * W + j];
-          orow[j] = s;
-        }
+        seg_join_rows(part, W, in.D, b, np, chunk, lane, [&](int64_t j, T s) { orow[j] = s; });
       } else {
         T* __restrict__ vrow = in.dv + (head * in.N + base + src) * in.Dv;
         T* __restrict__ krow = in.dk + (head * in.N + base + src) * in.D;
-        for (int j = lane; j < in.Dv + in.D; j += 64) {
-          T s = part[slot0 * W + j];
-          for (int64_t k = 1; k < np; ++k) s = s + part[at_slot(b, b + k * chunk, chunk) * W + j];
+        seg_join_rows(part, W, W, b, np, chunk, lane, [&](int64_t j, T s) {
           if (j < in.Dv) vrow[j] = s;
           else krow[j - in.Dv] = s;
-        }
+        });
       }
-    }
-  }
+    });
 }
 
 // ---- column pass: a sub-group of G lanes per (column, head); G = 64 is the wave form ------------------------------------------------
@@ -599,62 +562,43 @@ ag_col_kernel(AgIn<T, I> in, int64_t above, int64_t upto) {
   }
 }
 
-static unsigned ag_grid(int64_t items, int64_t per_block) {
-  return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(items, per_block), (int64_t)1 << 20));
-}
-
-#define AG_LAUNCH(kernel, grid, block, lds, ...)                          \
-  do {                                                                    \
-    hipLaunchKernelGGL((kernel), grid, block, lds, st, __VA_ARGS__);      \
-    if (int rc = launch_status()) return rc;                              \
-  } while (0)
-
 template <typename T, typename I, bool B, bool P>
 static int attention_grad_typed(AgIn<T, I> in, AtBias<T, B> bz, AtDrop<T, P> dz, int group, int col_group, int64_t short_max, int64_t chunk, int64_t max_row,
                                 int64_t max_col, hipStream_t st) {
   const unsigned gy = (unsigned)in.H;
   const int64_t nwin = ceil_div(in.nnz, chunk);
-  const dim3 pg(ag_grid(nwin, 4), gy);
+  const dim3 pg(seg_grid(nwin, 4), gy), wg(256);
   const AtBias<T, false> nob{};   // the launches that neither form a score nor hold z
   const AtDrop<T, false> nod{};   // the launches that neither form ed nor park pd
   if (in.M > 0) {   // the row pass; the short form always runs: it writes the dq rows of the rows without a stored element
-    const dim3 sg(ag_grid(in.M, 256 / group), gy);
-    if (group == 8) AG_LAUNCH((ag_short_kernel<T, I, 8, B, P>), sg, dim3(256), 0, in, short_max, AtMods<T, B, P>(bz, dz));
-    else if (group == 16) AG_LAUNCH((ag_short_kernel<T, I, 16, B, P>), sg, dim3(256), 0, in, short_max, AtMods<T, B, P>(bz, dz));
-    else if (group == 32) AG_LAUNCH((ag_short_kernel<T, I, 32, B, P>), sg, dim3(256), 0, in, short_max, AtMods<T, B, P>(bz, dz));
-    else AG_LAUNCH((ag_short_kernel<T, I, 64, B, P>), sg, dim3(256), 0, in, short_max, AtMods<T, B, P>(bz, dz));
+    SEG_GROUP(group, G, SPAMD_LAUNCH((ag_short_kernel<T, I, G, B, P>), dim3(seg_grid(in.M, 256 / G), gy), wg, 0, st, in, short_max, AtMods<T, B, P>(bz, dz)));
     if (std::min(max_row, chunk) > short_max)
-      AG_LAUNCH((ag_wide_kernel<T, I, B, P>), dim3(ag_grid(in.M, 64), gy), dim3(64), (size_t)(2 * chunk) * sizeof(T), in, short_max, chunk,
-                AtMods<T, B, P>(bz, dz));
+      SPAMD_LAUNCH((ag_wide_kernel<T, I, B, P>), dim3(seg_grid(in.M, 64), gy), dim3(64), (size_t)(2 * chunk) * sizeof(T), st, in, short_max, chunk,
+                   AtMods<T, B, P>(bz, dz));
     if (max_row > chunk) {
-      const dim3 jg(ag_grid(in.M, 256), gy);
-      AG_LAUNCH((ag_piece_kernel<T, I, 0, B, false>), pg, dim3(256), 0, in, chunk, nwin, AtMods<T, B, false>(bz, nod));
-      AG_LAUNCH((ag_join_kernel<T, I, 0>), jg, dim3(256), 0, in, chunk, nwin);
-      AG_LAUNCH((ag_piece_kernel<T, I, 1, false, false>), pg, dim3(256), 0, in, chunk, nwin, AtMods<T, false, false>(nob, nod));
-      AG_LAUNCH((ag_join_kernel<T, I, 1>), jg, dim3(256), 0, in, chunk, nwin);
-      AG_LAUNCH((ag_piece_kernel<T, I, 2, false, P>), pg, dim3(256), 0, in, chunk, nwin, AtMods<T, false, P>(nob, dz));
-      AG_LAUNCH((ag_join_kernel<T, I, 2>), jg, dim3(256), 0, in, chunk, nwin);
-      AG_LAUNCH((ag_piece_kernel<T, I, 3, B, P>), pg, dim3(256), 0, in, chunk, nwin, AtMods<T, B, P>(bz, dz));
-      AG_LAUNCH((ag_piece_kernel<T, I, 4, false, false>), pg, dim3(256), 0, in, chunk, nwin, AtMods<T, false, false>(nob, nod));
-      AG_LAUNCH((ag_join_kernel<T, I, 3>), jg, dim3(256), 0, in, chunk, nwin);
+      const dim3 jg(seg_grid(in.M, 256), gy);
+      SPAMD_LAUNCH((ag_piece_kernel<T, I, 0, B, false>), pg, wg, 0, st, in, chunk, nwin, AtMods<T, B, false>(bz, nod));
+      SPAMD_LAUNCH((ag_join_kernel<T, I, 0>), jg, wg, 0, st, in, chunk, nwin);
+      SPAMD_LAUNCH((ag_piece_kernel<T, I, 1, false, false>), pg, wg, 0, st, in, chunk, nwin, AtMods<T, false, false>(nob, nod));
+      SPAMD_LAUNCH((ag_join_kernel<T, I, 1>), jg, wg, 0, st, in, chunk, nwin);
+      SPAMD_LAUNCH((ag_piece_kernel<T, I, 2, false, P>), pg, wg, 0, st, in, chunk, nwin, AtMods<T, false, P>(nob, dz));
+      SPAMD_LAUNCH((ag_join_kernel<T, I, 2>), jg, wg, 0, st, in, chunk, nwin);
+      SPAMD_LAUNCH((ag_piece_kernel<T, I, 3, B, P>), pg, wg, 0, st, in, chunk, nwin, AtMods<T, B, P>(bz, dz));
+      SPAMD_LAUNCH((ag_piece_kernel<T, I, 4, false, false>), pg, wg, 0, st, in, chunk, nwin, AtMods<T, false, false>(nob, nod));
+      SPAMD_LAUNCH((ag_join_kernel<T, I, 3>), jg, wg, 0, st, in, chunk, nwin);
     }
   }
   if (in.N > 0 && (in.D > 0 || in.Dv > 0)) {   // the column pass; its first launch writes the empty columns
-    const dim3 cg(ag_grid(in.N, 256 / col_group), gy);
-    if (col_group == 8) AG_LAUNCH((ag_col_kernel<T, I, 8>), cg, dim3(256), 0, in, (int64_t)-1, short_max);
-    else if (col_group == 16) AG_LAUNCH((ag_col_kernel<T, I, 16>), cg, dim3(256), 0, in, (int64_t)-1, short_max);
-    else if (col_group == 32) AG_LAUNCH((ag_col_kernel<T, I, 32>), cg, dim3(256), 0, in, (int64_t)-1, short_max);
-    else AG_LAUNCH((ag_col_kernel<T, I, 64>), cg, dim3(256), 0, in, (int64_t)-1, short_max);
+    SEG_GROUP(col_group, G, SPAMD_LAUNCH((ag_col_kernel<T, I, G>), dim3(seg_grid(in.N, 256 / G), gy), wg, 0, st, in, (int64_t)-1, short_max));
     if (std::min(max_col, chunk) > short_max)
-      AG_LAUNCH((ag_col_kernel<T, I, 64>), dim3(ag_grid(in.N, 4), gy), dim3(256), 0, in, short_max, chunk);
+      SPAMD_LAUNCH((ag_col_kernel<T, I, 64>), dim3(seg_grid(in.N, 4), gy), wg, 0, st, in, short_max, chunk);
     if (max_col > chunk) {
-      AG_LAUNCH((ag_piece_kernel<T, I, 5, false, false>), pg, dim3(256), 0, in, chunk, nwin, AtMods<T, false, false>(nob, nod));
-      AG_LAUNCH((ag_join_kernel<T, I, 4>), dim3(ag_grid(in.N, 256), gy), dim3(256), 0, in, chunk, nwin);
+      SPAMD_LAUNCH((ag_piece_kernel<T, I, 5, false, false>), pg, wg, 0, st, in, chunk, nwin, AtMods<T, false, false>(nob, nod));
+      SPAMD_LAUNCH((ag_join_kernel<T, I, 4>), dim3(seg_grid(in.N, 256), gy), wg, 0, st, in, chunk, nwin);
     }
   }
   return 0;
 }
-#undef AG_LAUNCH
 
 struct AgArgs {
   int64_t M, N, nnz, H, D, Dv;
@@ -708,7 +652,7 @@ using namespace spamd;
 extern "C" int64_t spamd_attention_grad_ws_bytes(int val_dtype, int64_t nnz, int64_t H, int64_t D, int64_t Dv, int64_t chunk) {
   const int64_t esz = val_dtype == SPAMD_F32 ? 4 : (val_dtype == SPAMD_F64 ? 8 : 0);
   if (!esz) return SPAMD_ETYPE;
-  if (nnz < 0 || H < 0 || D < 0 || Dv < 0 || chunk < 64 || chunk > ATTENTION_MAX_CHUNK || chunk % 64) return SPAMD_EINVAL;
+  if (nnz < 0 || H < 0 || D < 0 || Dv < 0 || !seg_chunk_ok(chunk, ATTENTION_MAX_CHUNK)) return SPAMD_EINVAL;
   return H * ag_ws_values(nnz, nnz > chunk ? ceil_div(nnz, chunk) : 0, D, Dv) * esz;
 }
 
@@ -733,9 +677,7 @@ extern "C" int spamd_attention_grad_dropout(int val_dtype, int idx_dtype, int64_
     return SPAMD_EINVAL;
   if (bias_head < 0) return SPAMD_EINVAL;
   if (!dropout_rate_ok(rate) || head0 < 0) return SPAMD_EINVAL;
-  if (group != 8 && group != 16 && group != 32 && group != 64) return SPAMD_EINVAL;
-  if (col_group != 8 && col_group != 16 && col_group != 32 && col_group != 64) return SPAMD_EINVAL;
-  if (chunk < 64 || chunk > ATTENTION_MAX_CHUNK || chunk % 64 || short_max < 0 || short_max > 64) return SPAMD_EINVAL;
+  if (!seg_params_ok(group, chunk, ATTENTION_MAX_CHUNK, short_max) || !seg_group_ok(col_group)) return SPAMD_EINVAL;
   const bool has_dq = M > 0 && D > 0, has_dk = N > 0 && D > 0, has_dv = N > 0 && Dv > 0;
   if (H == 0 || !(has_dq || has_dk || has_dv)) return 0;   // nothing to write
   if ((has_dq && !dq) || (has_dk && !dk) || (has_dv && !dv)) return SPAMD_EINVAL;

@@ -228,6 +228,13 @@ inline int launch_status() {
   return (int)e;
 }
 
+// launch on the stream `st`, and leave the calling function with the error code if the launch failed
+#define SPAMD_LAUNCH(kernel, grid, block, lds, st, ...)                 \
+  do {                                                                  \
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, __VA_ARGS__);      \
+    if (int rc = launch_status()) return rc;                            \
+  } while (0)
+
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 #ifdef __HIPCC__

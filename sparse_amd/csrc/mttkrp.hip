@@ -18,17 +18,13 @@
 //
 // Launches:
 //   1. mttkrp_kernel, two block ranges.  Row blocks: one sub-group per row; rows of at most `chunk` elements are finished
-//      (empty rows store +0.0), longer rows are left alone.  Window blocks (only when nnz > chunk): sub-group g looks at the
-//      plan positions [g * chunk, (g + 1) * chunk).  A row of more than `chunk` elements spans more than a window, so at
-//      most two pieces of such rows START inside one: piece k >= 0 of the row that holds the window's first position
-//      (workspace slot 2g) and piece 0 of the row that holds its last position, if that is another row (slot 2g + 1).  The
-//      sub-group finds both with two binary searches over rowptr and writes their sums to the workspace - no piece list, no
-//      count brought back to the host.
+//      (empty rows store +0.0), longer rows are left alone.  Window blocks (only when nnz > chunk): sub-group g walks the
+//      window g of `chunk` plan positions (csrc/segment_walk.h): at most two pieces of longer rows START inside it, found
+//      with two binary searches over rowptr; their sums go to the workspace slots 2g and 2g + 1 - no piece list, no count
+//      brought back to the host.
 //   2. mttkrp_join_kernel (only when nnz > chunk): one sub-group per row; a row of more than `chunk` elements adds its
 //      piece sums in piece order and stores the result.
-#include "common.h"
-
-#include <algorithm>
+#include "segments.h"
 
 #define MTTKRP_MAX_NDIM 8
 
@@ -125,17 +121,6 @@ __device__ __forceinline__ void mt_piece_to(const MtArgs<T, I>& a, const T* __re
   }
 }
 
-// last r in [0, nrows] with rowptr[r] <= pos (rowptr[0] = 0 <= pos)
-__device__ __forceinline__ int64_t mt_row_of(const int64_t* __restrict__ rowptr, int64_t nrows, int64_t pos) {
-  int64_t lo = 0, hi = nrows;   // invariant: rowptr[lo] <= pos; the answer is in [lo, hi]
-  while (lo < hi) {
-    const int64_t mid = lo + (hi - lo + 1) / 2;
-    if (rowptr[mid] <= pos) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
 template <typename T, typename I, bool EXACT, int NF, int G, int CPL>
 __global__ void __launch_bounds__(256)
 mttkrp_kernel(MtArgs<T, I> a, int64_t nnz, int64_t nrows, int64_t R, const T* __restrict__ data,
@@ -154,25 +139,10 @@ mttkrp_kernel(MtArgs<T, I> a, int64_t nnz, int64_t nrows, int64_t R, const T* __
   }
   const int64_t nwin = (nnz + chunk - 1) / chunk;
   const int64_t win_blocks = (int64_t)gridDim.x - row_blocks;
-  for (int64_t g = ((int64_t)blockIdx.x - row_blocks) * GPB + gib; g < nwin; g += win_blocks * GPB) {
-    const int64_t lo = g * chunk;
-    const int64_t hi = lo + chunk < nnz ? lo + chunk : nnz;
-    const int64_t r0 = mt_row_of(rowptr, nrows, lo);   // holds position lo (lo < nnz: r0 < nrows, the row is not empty)
-    {
-      const int64_t b0 = rowptr[r0], e0 = rowptr[r0 + 1];
-      if (e0 - b0 > chunk) {
-        const int64_t k = (lo - b0 + chunk - 1) / chunk;
-        const int64_t s = b0 + k * chunk;   // the one piece start of this row in [lo, lo + chunk)
-        if (s < hi && s < e0)
-          mt_piece_to<T, I, EXACT, NF, G, CPL>(a, data, perm, s, s + chunk < e0 ? s + chunk : e0, sub, R, ws + (2 * g) * R);
-      }
-    }
-    const int64_t r1 = mt_row_of(rowptr, nrows, hi - 1);
-    if (r1 > r0) {   // starts inside the window; only the last such row can be longer than the window
-      const int64_t b1 = rowptr[r1], e1 = rowptr[r1 + 1];
-      if (e1 - b1 > chunk) mt_piece_to<T, I, EXACT, NF, G, CPL>(a, data, perm, b1, b1 + chunk, sub, R, ws + (2 * g + 1) * R);
-    }
-  }
+  for (int64_t g = ((int64_t)blockIdx.x - row_blocks) * GPB + gib; g < nwin; g += win_blocks * GPB)
+    seg_window_pieces(rowptr, nrows, nnz, chunk, g, [&](int64_t, int64_t b, int64_t s, int64_t e) {
+      mt_piece_to<T, I, EXACT, NF, G, CPL>(a, data, perm, s, e, sub, R, ws + seg_slot(b, s, chunk) * R);
+    });
 }
 
 template <typename T, int G>
@@ -186,10 +156,8 @@ mttkrp_join_kernel(int64_t nrows, int64_t R, const int64_t* __restrict__ rowptr,
     const int64_t b = rowptr[row], e = rowptr[row + 1];
     if (e - b <= chunk) continue;
     for (int64_t r = sub; r < R; r += G) {
-      // piece 0 starts at b: slot 2g when b is a window's first position, else 2g + 1; every later piece is the first one
-      // that starts in its window
-      T s = ws[(2 * (b / chunk) + (b % chunk != 0 ? 1 : 0)) * R + r];
-      for (int64_t p = b + chunk; p < e; p += chunk) s = s + ws[(2 * (p / chunk)) * R + r];
+      T s = ws[seg_slot(b, b, chunk) * R + r];
+      for (int64_t p = b + chunk; p < e; p += chunk) s = s + ws[seg_slot(b, p, chunk) * R + r];
       out[row * ldo + r] = s;
     }
   }
@@ -199,18 +167,13 @@ template <typename T, typename I, bool EXACT, int NF, int G, int CPL>
 static int launch_mttkrp_as(const MtArgs<T, I>& a, int64_t nnz, int64_t nrows, int64_t R, const T* data, const int64_t* perm,
                             const int64_t* rowptr, int64_t chunk, T* ws, T* out, int64_t ldo, hipStream_t st) {
   constexpr int GPB = 256 / G;
-  const int64_t cap = (int64_t)1 << 20;
-  const int64_t row_blocks = std::min(ceil_div(nrows, GPB), cap);
+  const int64_t row_blocks = seg_grid(nrows, GPB);   // (nrows > 0: the entry returns before)
   const bool pieces = nnz > chunk;
-  const int64_t win_blocks = pieces ? std::min(ceil_div(ceil_div(nnz, chunk), GPB), cap) : 0;
-  hipLaunchKernelGGL((mttkrp_kernel<T, I, EXACT, NF, G, CPL>), dim3((unsigned)(row_blocks + win_blocks)), dim3(256), 0, st, a, nnz,
-                     nrows, R, data, perm, rowptr, chunk, row_blocks, ws, out, ldo);
-  if (int rc = launch_status()) return rc;
-  if (pieces) {
-    hipLaunchKernelGGL((mttkrp_join_kernel<T, G>), dim3((unsigned)row_blocks), dim3(256), 0, st, nrows, R, rowptr, chunk,
-                       (const T*)ws, out, ldo);
-    return launch_status();
-  }
+  const int64_t win_blocks = pieces ? seg_grid(ceil_div(nnz, chunk), GPB) : 0;
+  SPAMD_LAUNCH((mttkrp_kernel<T, I, EXACT, NF, G, CPL>), dim3((unsigned)(row_blocks + win_blocks)), dim3(256), 0, st, a, nnz, nrows, R, data,
+               perm, rowptr, chunk, row_blocks, ws, out, ldo);
+  if (pieces)
+    SPAMD_LAUNCH((mttkrp_join_kernel<T, G>), dim3((unsigned)row_blocks), dim3(256), 0, st, nrows, R, rowptr, chunk, (const T*)ws, out, ldo);
   return 0;
 }
 
@@ -246,9 +209,8 @@ static int mttkrp_typed(int ndim, int mode, int64_t nnz, int64_t R, const void* 
                         int64_t nrows, int64_t chunk, void* ws, void* out, int64_t ldo, unsigned flags, hipStream_t st) {
   if (nnz == 0) {
     const int64_t n = nrows * R;
-    hipLaunchKernelGGL((mttkrp_zero_kernel<T>), dim3((unsigned)std::min<int64_t>(ceil_div(n, 256), 65536)), dim3(256), 0, st, nrows,
-                       R, (T*)out, ldo);
-    return launch_status();
+    SPAMD_LAUNCH((mttkrp_zero_kernel<T>), dim3(seg_grid(n, 256, 65536)), dim3(256), 0, st, nrows, R, (T*)out, ldo);
+    return 0;
   }
   MtArgs<T, I> a;
   a.nf = 0;

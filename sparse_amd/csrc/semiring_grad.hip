@@ -72,7 +72,7 @@ sg_elem_kernel(SgIn<T, I> p) {
   for (int64_t w = (int64_t)blockIdx.x * SPB + threadIdx.x / G; w < nwin; w += (int64_t)gridDim.x * SPB) {
     const int64_t lo = w * SG_WINDOW;
     const int64_t hi = lo + SG_WINDOW < p.nnz ? lo + SG_WINDOW : p.nnz;
-    int64_t row = at_row_of(p.ptr, p.M, lo);   // lo < nnz: row < M and the row is not empty
+    int64_t row = seg_of(p.ptr, p.M, lo);   // lo < nnz: row < M and the row is not empty
     int64_t row_end = (int64_t)p.ptr[row + 1];
     bool fresh = true;
     int64_t ar[V];
@@ -269,12 +269,12 @@ sg_col_lane_kernel(SgIn<T, I> p, int64_t upto) {
 }
 
 // a wave per window of `chunk` positions of the column order: the window holds at most two piece starts of long columns
-// (csrc/attention.hip) - workspace rows 2g and 2g + 1 of N values
+// (csrc/segment_walk.h) - workspace rows 2g and 2g + 1 of N values
 template <typename T, typename I, bool TIMES>
 __device__ __forceinline__ void sg_piece(const SgIn<T, I>& p, int64_t k, int64_t b, int64_t s, int64_t e, int64_t chunk, int lane,
                                          T* __restrict__ part) {
   constexpr int VEC = SgVec<T>::N;
-  const int64_t slot = at_slot(b, s, chunk);
+  const int64_t slot = seg_slot(b, s, chunk);
   for (int64_t c0 = 0; c0 < p.N; c0 += (int64_t)64 * VEC) {
     const int64_t col = c0 + (int64_t)lane * VEC;
     T acc[VEC];
@@ -291,23 +291,10 @@ template <typename T, typename I, bool TIMES>
 __global__ void __launch_bounds__(256)
 sg_piece_kernel(SgIn<T, I> p, int64_t chunk, int64_t nwin, T* __restrict__ part) {
   const int lane = threadIdx.x & 63;
-  for (int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); g < nwin; g += (int64_t)gridDim.x * 4) {
-    const int64_t lo = g * chunk;
-    const int64_t hi = lo + chunk < p.nnz ? lo + chunk : p.nnz;
-    const int64_t k0 = at_row_of(p.cptr, p.K, lo);   // lo < nnz: k0 < K and the column is not empty
-    {
-      const int64_t b0 = (int64_t)p.cptr[k0], e0 = (int64_t)p.cptr[k0 + 1];
-      if (e0 - b0 > chunk) {
-        const int64_t s = b0 + (lo - b0 + chunk - 1) / chunk * chunk;   // the one piece start of this column in [lo, lo + chunk)
-        if (s < hi && s < e0) sg_piece<T, I, TIMES>(p, k0, b0, s, s + chunk < e0 ? s + chunk : e0, chunk, lane, part);
-      }
-    }
-    const int64_t k1 = at_row_of(p.cptr, p.K, hi - 1);
-    if (k1 > k0) {   // starts inside the window; only the last such column can be longer than the window
-      const int64_t b1 = (int64_t)p.cptr[k1], e1 = (int64_t)p.cptr[k1 + 1];
-      if (e1 - b1 > chunk) sg_piece<T, I, TIMES>(p, k1, b1, b1, b1 + chunk, chunk, lane, part);
-    }
-  }
+  for (int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); g < nwin; g += (int64_t)gridDim.x * 4)
+    seg_window_pieces(p.cptr, p.K, p.nnz, chunk, g, [&](int64_t k, int64_t b, int64_t s, int64_t e) {
+      sg_piece<T, I, TIMES>(p, k, b, s, e, chunk, lane, part);
+    });
 }
 
 // the piece sums of every long column added one after the other in piece order, the first piece's sum being the start
@@ -317,69 +304,37 @@ sg_join_kernel(SgIn<T, I> p, int64_t chunk, const T* __restrict__ part) {
 #pragma clang fp contract(off)
   const int lane = threadIdx.x & 63;
   const int64_t nwaves = (int64_t)gridDim.x * 4;
-  for (int64_t base = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64; base < p.K; base += nwaves * 64) {
-    const int64_t mine = base + lane;
-    int64_t mb = 0, mn = 0;
-    if (mine < p.K) {
-      mb = (int64_t)p.cptr[mine];
-      mn = (int64_t)p.cptr[mine + 1] - mb;
-    }
-    unsigned long long todo = __ballot(mn > chunk);
-    while (todo) {   // wave-uniform: all 64 lanes stay together
-      const int src = __builtin_ctzll(todo);
-      todo &= todo - 1;
-      const int64_t b = wave_bcast(mb, src), n = wave_bcast(mn, src);
-      const int64_t np = (n + chunk - 1) / chunk;
-      const int64_t slot0 = at_slot(b, b, chunk);
+  for (int64_t base = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64; base < p.K; base += nwaves * 64)
+    seg_wave_each(p.cptr, p.K, base, lane, [&](int64_t len) { return len > chunk; }, [&](int src, int64_t b, int64_t n) {
       T* __restrict__ orow = p.db + (base + src) * p.lddb;
-      for (int64_t j = lane; j < p.N; j += 64) {
-        T s = part[slot0 * p.N + j];
-        for (int64_t q = 1; q < np; ++q) s = s + part[at_slot(b, b + q * chunk, chunk) * p.N + j];
-        orow[j] = s;
-      }
-    }
-  }
-}
-
-static unsigned sg_grid(int64_t items, int64_t per_block) {
-  return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(items, per_block), (int64_t)1 << 20));
+      seg_join_rows(part, p.N, p.N, b, (n + chunk - 1) / chunk, chunk, lane, [&](int64_t j, T s) { orow[j] = s; });
+    });
 }
 
 static int64_t sg_ws_bytes(int64_t esz, int64_t nnz, int64_t N, int64_t chunk) {
   return 2 * ceil_div(nnz, chunk) * N * esz;
 }
 
-#define SG_LAUNCH(kernel, grid, ...)                                      \
-  do {                                                                    \
-    hipLaunchKernelGGL((kernel), grid, dim3(256), 0, st, __VA_ARGS__);    \
-    if (int rc = launch_status()) return rc;                              \
-  } while (0)
-
 template <typename T, typename I, bool TIMES>
 static int semiring_grad_typed(SgIn<T, I> p, int group, int col_group, int64_t short_max, int64_t chunk, int64_t max_col, void* ws,
                                hipStream_t st) {
-  if (p.da && p.nnz > 0) {
-    const dim3 eg(sg_grid(ceil_div(p.nnz, SG_WINDOW), 256 / group));
-    if (group == 8) SG_LAUNCH((sg_elem_kernel<T, I, TIMES, 8>), eg, p);
-    else if (group == 16) SG_LAUNCH((sg_elem_kernel<T, I, TIMES, 16>), eg, p);
-    else if (group == 32) SG_LAUNCH((sg_elem_kernel<T, I, TIMES, 32>), eg, p);
-    else SG_LAUNCH((sg_elem_kernel<T, I, TIMES, 64>), eg, p);
-  }
-  if (p.dinit && p.M > 0 && p.N > 0) SG_LAUNCH((sg_init_kernel<T, I>), dim3(sg_grid(p.M * p.N, 256)), p);
+  const dim3 wg(256);
+  if (p.da && p.nnz > 0)
+    SEG_GROUP(group, G, SPAMD_LAUNCH((sg_elem_kernel<T, I, TIMES, G>), dim3(seg_grid(ceil_div(p.nnz, SG_WINDOW), 256 / G)), wg, 0, st, p));
+  if (p.dinit && p.M > 0 && p.N > 0) SPAMD_LAUNCH((sg_init_kernel<T, I>), dim3(seg_grid(p.M * p.N, 256)), wg, 0, st, p);
   if (p.db && p.K > 0 && p.N > 0) {   // the first launch writes the columns without a stored element
-    if (col_group == 1) SG_LAUNCH((sg_col_lane_kernel<T, I, TIMES>), dim3(sg_grid(p.K, 256)), p, short_max);
-    else SG_LAUNCH((sg_col_kernel<T, I, TIMES>), dim3(sg_grid(p.K, 256 / col_group)), p, col_group, (int64_t)-1, short_max);
+    if (col_group == 1) SPAMD_LAUNCH((sg_col_lane_kernel<T, I, TIMES>), dim3(seg_grid(p.K, 256)), wg, 0, st, p, short_max);
+    else SPAMD_LAUNCH((sg_col_kernel<T, I, TIMES>), dim3(seg_grid(p.K, 256 / col_group)), wg, 0, st, p, col_group, (int64_t)-1, short_max);
     if (std::min(max_col, chunk) > short_max)
-      SG_LAUNCH((sg_col_kernel<T, I, TIMES>), dim3(sg_grid(p.K, 4)), p, 64, short_max, chunk);
+      SPAMD_LAUNCH((sg_col_kernel<T, I, TIMES>), dim3(seg_grid(p.K, 4)), wg, 0, st, p, 64, short_max, chunk);
     if (max_col > chunk) {
       const int64_t nwin = ceil_div(p.nnz, chunk);
-      SG_LAUNCH((sg_piece_kernel<T, I, TIMES>), dim3(sg_grid(nwin, 4)), p, chunk, nwin, (T*)ws);
-      SG_LAUNCH((sg_join_kernel<T, I>), dim3(sg_grid(p.K, 256)), p, chunk, (const T*)ws);
+      SPAMD_LAUNCH((sg_piece_kernel<T, I, TIMES>), dim3(seg_grid(nwin, 4)), wg, 0, st, p, chunk, nwin, (T*)ws);
+      SPAMD_LAUNCH((sg_join_kernel<T, I>), dim3(seg_grid(p.K, 256)), wg, 0, st, p, chunk, (const T*)ws);
     }
   }
   return 0;
 }
-#undef SG_LAUNCH
 
 struct SgArgs {
   int mul;
@@ -420,7 +375,7 @@ static int64_t sg_esz(int val_dtype) {
 extern "C" int64_t spamd_semiring_grad_ws_bytes(int val_dtype, int64_t nnz, int64_t N, int64_t chunk) {
   const int64_t esz = sg_esz(val_dtype);
   if (!esz) return SPAMD_ETYPE;
-  if (nnz < 0 || N < 0 || chunk < 64 || chunk > SG_MAX_CHUNK || chunk % 64) return SPAMD_EINVAL;
+  if (nnz < 0 || N < 0 || !seg_chunk_ok(chunk, SG_MAX_CHUNK)) return SPAMD_EINVAL;
   if (nnz <= chunk) return 0;
   return sg_ws_bytes(esz, nnz, N, chunk);
 }
@@ -436,11 +391,8 @@ extern "C" int spamd_semiring_grad(int val_dtype, int idx_dtype, int mul, int64_
   if (mul != SPAMD_SEMIRING_PLUS && mul != SPAMD_SEMIRING_TIMES) return SPAMD_EINVAL;
   const bool times = mul == SPAMD_SEMIRING_TIMES;
   if (M < 0 || K < 0 || N < 0 || nnz < 0 || max_col < 0 || max_col > nnz) return SPAMD_EINVAL;
-  if (group != 8 && group != 16 && group != 32 && group != 64) return SPAMD_EINVAL;
-  if (col_group != 1 && col_group != 8 && col_group != 16 && col_group != 32 && col_group != 64) return SPAMD_EINVAL;
+  if (!seg_params_ok(group, chunk, SG_MAX_CHUNK, short_max) || (col_group != 1 && !seg_group_ok(col_group))) return SPAMD_EINVAL;
   if (col_group == 1 && N > SG_LANE_MAX_N) return SPAMD_EINVAL;
-  if (short_max < 0 || short_max > 64) return SPAMD_EINVAL;
-  if (chunk < 64 || chunk > SG_MAX_CHUNK || chunk % 64) return SPAMD_EINVAL;
   if (lda < N || ldg < N || (times && ldb < N) || (db && lddb < N) || (dinit && lddi < N)) return SPAMD_EINVAL;
   const bool elem = da && nnz > 0, cols = db && K > 0 && N > 0, init = dinit && M > 0 && N > 0;
   if (!elem && !cols && !init) return 0;

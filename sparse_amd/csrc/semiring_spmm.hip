@@ -24,8 +24,8 @@
 //          broadcast; every lane folds its columns over them in stored order (ordered states in registers), four b rows in flight.
 //   lanes  narrow results: G lanes own one output (i, j) and run ALONG the row, lane u folds the elements u, u + G, .. (four
 //          gathers of b in flight), then a butterfly over placed states.  Bound by the gather of b[k].
-//   long   rows longer than `chunk`: pieces of `chunk` elements, one wave each, found as csrc/softmax.hip finds its pieces (at most
-//          two piece starts per window of `chunk` positions: workspace slots 2g and 2g + 1).  A piece is folded in the lanes shape
+//   long   rows longer than `chunk`: pieces of `chunk` elements, one wave each, found by windows of `chunk` positions (csrc/segment_walk.h:
+//          at most two piece starts per window, workspace slots 2g and 2g + 1).  A piece is folded in the lanes shape
 //          (narrow) or by 64 / G sub-groups in the rows shape over consecutive parts of it, joined in order.  Piece states go to
 //          the workspace; a join launch - it starts after the piece launch has ENDED - folds them in piece order after the init.
 #include "attention_common.h"
@@ -38,6 +38,7 @@ namespace spamd {
 constexpr int SR_EMPTY = -2;                                     // the k of an ordered state that holds nothing (-1: the init)
 constexpr int SR_NOPOS = std::numeric_limits<int>::max();        // the position of a placed state that holds nothing
 constexpr int64_t SR_MAX_CHUNK = (int64_t)1 << 30;
+constexpr int64_t SR_GRID_CAP = (int64_t)1 << 16;                // workgroups per launch (the other segment walkers: 2^20)
 
 template <typename T, bool MAX>
 __device__ __forceinline__ T sr_identity() {
@@ -294,7 +295,7 @@ sr_lanes_kernel(SrIn<T, I> p, int G, int64_t upto) {
 template <typename T, typename I, bool MAX, bool TIMES, bool ARG, bool NARROW>
 __device__ __forceinline__ void sr_piece(const SrIn<T, I>& p, int64_t b, int64_t s, int64_t e, int64_t chunk, int64_t nslots,
                                          int G, int lane, T* __restrict__ wsv, int64_t* __restrict__ wsa) {
-  const int64_t slot = at_slot(b, s, chunk);
+  const int64_t slot = seg_slot(b, s, chunk);
   if constexpr (NARROW) {
     for (int64_t j = 0; j < p.N; ++j) {
       T val;
@@ -352,24 +353,10 @@ __global__ void __launch_bounds__(256)
 sr_piece_kernel(SrIn<T, I> p, int64_t nnz, int64_t chunk, int64_t nwin, int64_t nslots, int G, T* __restrict__ wsv,
                 int64_t* __restrict__ wsa) {
   const int lane = threadIdx.x & 63;
-  for (int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); g < nwin; g += (int64_t)gridDim.x * 4) {
-    const int64_t lo = g * chunk;
-    const int64_t hi = lo + chunk < nnz ? lo + chunk : nnz;
-    const int64_t r0 = at_row_of(p.ptr, p.M, lo);   // lo < nnz: r0 < M and the row is not empty
-    {
-      const int64_t b0 = (int64_t)p.ptr[r0], e0 = (int64_t)p.ptr[r0 + 1];
-      if (e0 - b0 > chunk) {
-        const int64_t s = b0 + (lo - b0 + chunk - 1) / chunk * chunk;   // the one piece start of this row in [lo, lo + chunk)
-        if (s < hi && s < e0)
-          sr_piece<T, I, MAX, TIMES, ARG, NARROW>(p, b0, s, s + chunk < e0 ? s + chunk : e0, chunk, nslots, G, lane, wsv, wsa);
-      }
-    }
-    const int64_t r1 = at_row_of(p.ptr, p.M, hi - 1);
-    if (r1 > r0) {   // starts inside the window; only the last such row can be longer than the window
-      const int64_t b1 = (int64_t)p.ptr[r1], e1 = (int64_t)p.ptr[r1 + 1];
-      if (e1 - b1 > chunk) sr_piece<T, I, MAX, TIMES, ARG, NARROW>(p, b1, b1, b1 + chunk, chunk, nslots, G, lane, wsv, wsa);
-    }
-  }
+  for (int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); g < nwin; g += (int64_t)gridDim.x * 4)
+    seg_window_pieces(p.ptr, p.M, nnz, chunk, g, [&](int64_t, int64_t b, int64_t s, int64_t e) {
+      sr_piece<T, I, MAX, TIMES, ARG, NARROW>(p, b, s, e, chunk, nslots, G, lane, wsv, wsa);
+    });
 }
 
 // the piece states of every long row folded in piece order after the init: lanes along the pieces, placed by piece number
@@ -378,25 +365,15 @@ __global__ void __launch_bounds__(256)
 sr_join_kernel(SrIn<T, I> p, int64_t chunk, int64_t nslots, const T* __restrict__ wsv, const int64_t* __restrict__ wsa) {
   const int lane = threadIdx.x & 63;
   const int64_t nwaves = (int64_t)gridDim.x * 4;
-  for (int64_t base = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64; base < p.M; base += nwaves * 64) {
-    const int64_t r = base + lane;
-    int64_t mb = 0, mn = 0;
-    if (r < p.M) {
-      mb = (int64_t)p.ptr[r];
-      mn = (int64_t)p.ptr[r + 1] - mb;
-    }
-    unsigned long long todo = __ballot(mn > chunk);
-    while (todo) {   // wave-uniform: all 64 lanes stay together
-      const int src = __builtin_ctzll(todo);
-      todo &= todo - 1;
+  for (int64_t base = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64; base < p.M; base += nwaves * 64)
+    seg_wave_each(p.ptr, p.M, base, lane, [&](int64_t len) { return len > chunk; }, [&](int src, int64_t b, int64_t n) {
       const int64_t row = base + src;
-      const int64_t b = wave_bcast(mb, src), n = wave_bcast(mn, src);
       const int64_t np = (n + chunk - 1) / chunk;
       for (int64_t j = 0; j < p.N; ++j) {
         T val = sr_identity<T, MAX>();
         int pos = SR_NOPOS;
         for (int64_t k = lane; k < np; k += 64) {
-          const T t = wsv[j * nslots + at_slot(b, b + k * chunk, chunk)];
+          const T t = wsv[j * nslots + seg_slot(b, b + k * chunk, chunk)];
           const bool take = pos == SR_NOPOS || sr_takes<T, MAX>(t, val);
           val = take ? t : val;
           pos = take ? (int)k : pos;
@@ -411,15 +388,10 @@ sr_join_kernel(SrIn<T, I> p, int64_t chunk, int64_t nslots, const T* __restrict_
         if (lane == 0) {
           sr_finish<T, MAX>(p.init ? p.init + row * p.ldi + j : nullptr, val, pos);
           p.out[row * p.ldo + j] = val;
-          if constexpr (ARG) p.arg[row * p.lda + j] = pos < 0 ? (int64_t)-1 : wsa[j * nslots + at_slot(b, b + (int64_t)pos * chunk, chunk)];
+          if constexpr (ARG) p.arg[row * p.lda + j] = pos < 0 ? (int64_t)-1 : wsa[j * nslots + seg_slot(b, b + (int64_t)pos * chunk, chunk)];
         }
       }
-    }
-  }
-}
-
-static unsigned sr_grid(int64_t items, int64_t per_block) {
-  return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(items, per_block), (int64_t)1 << 16));
+    });
 }
 
 static int64_t sr_ws_bytes(int64_t esz, int64_t nnz, int64_t N, int64_t chunk, int with_arg) {
@@ -429,24 +401,17 @@ static int64_t sr_ws_bytes(int64_t esz, int64_t nnz, int64_t N, int64_t chunk, i
 template <typename T, typename I, bool MAX, bool TIMES, bool ARG>
 static int semiring_typed(SrIn<T, I> p, int64_t nnz, int narrow, int group, int64_t chunk, int64_t max_len, void* ws, hipStream_t st) {
   const int rpw = 64 / group;
-  if (narrow)
-    hipLaunchKernelGGL((sr_lanes_kernel<T, I, MAX, TIMES, ARG>), dim3(sr_grid(p.M * p.N, 4 * rpw)), dim3(256), 0, st, p, group, chunk);
-  else
-    hipLaunchKernelGGL((sr_rows_kernel<T, I, MAX, TIMES, ARG>), dim3(sr_grid(p.M, 4 * rpw)), dim3(256), 0, st, p, group, chunk);
-  if (int rc = launch_status()) return rc;
+  const dim3 wg(256);
+  if (narrow) SPAMD_LAUNCH((sr_lanes_kernel<T, I, MAX, TIMES, ARG>), dim3(seg_grid(p.M * p.N, 4 * rpw, SR_GRID_CAP)), wg, 0, st, p, group, chunk);
+  else SPAMD_LAUNCH((sr_rows_kernel<T, I, MAX, TIMES, ARG>), dim3(seg_grid(p.M, 4 * rpw, SR_GRID_CAP)), wg, 0, st, p, group, chunk);
   if (max_len > chunk) {
     const int64_t nwin = ceil_div(nnz, chunk), nslots = 2 * nwin;
     int64_t* wsa = ARG ? (int64_t*)ws : nullptr;
     T* wsv = (T*)((char*)ws + (ARG ? 8 * p.N * nslots : 0));
-    if (narrow)
-      hipLaunchKernelGGL((sr_piece_kernel<T, I, MAX, TIMES, ARG, true>), dim3(sr_grid(nwin, 4)), dim3(256), 0, st, p, nnz, chunk, nwin,
-                         nslots, group, wsv, wsa);
-    else
-      hipLaunchKernelGGL((sr_piece_kernel<T, I, MAX, TIMES, ARG, false>), dim3(sr_grid(nwin, 4)), dim3(256), 0, st, p, nnz, chunk, nwin,
-                         nslots, group, wsv, wsa);
-    if (int rc = launch_status()) return rc;
-    hipLaunchKernelGGL((sr_join_kernel<T, I, MAX, ARG>), dim3(sr_grid(p.M, 256)), dim3(256), 0, st, p, chunk, nslots, wsv, wsa);
-    if (int rc = launch_status()) return rc;
+    const dim3 pg(seg_grid(nwin, 4, SR_GRID_CAP));
+    if (narrow) SPAMD_LAUNCH((sr_piece_kernel<T, I, MAX, TIMES, ARG, true>), pg, wg, 0, st, p, nnz, chunk, nwin, nslots, group, wsv, wsa);
+    else SPAMD_LAUNCH((sr_piece_kernel<T, I, MAX, TIMES, ARG, false>), pg, wg, 0, st, p, nnz, chunk, nwin, nslots, group, wsv, wsa);
+    SPAMD_LAUNCH((sr_join_kernel<T, I, MAX, ARG>), dim3(seg_grid(p.M, 256, SR_GRID_CAP)), wg, 0, st, p, chunk, nslots, wsv, wsa);
   }
   return 0;
 }
@@ -478,7 +443,7 @@ static int64_t sr_esz(int val_dtype) {
 extern "C" int64_t spamd_semiring_spmm_ws_bytes(int val_dtype, int64_t nnz, int64_t N, int64_t chunk, int with_arg) {
   const int64_t esz = sr_esz(val_dtype);
   if (!esz) return SPAMD_ETYPE;
-  if (nnz < 0 || N < 0 || chunk < 64 || chunk > SR_MAX_CHUNK || chunk % 64) return SPAMD_EINVAL;
+  if (nnz < 0 || N < 0 || !seg_chunk_ok(chunk, SR_MAX_CHUNK)) return SPAMD_EINVAL;
   if (nnz <= chunk) return 0;
   return sr_ws_bytes(esz, nnz, N, chunk, with_arg);
 }
@@ -493,8 +458,7 @@ extern "C" int spamd_semiring_spmm(int val_dtype, int idx_dtype, int add, int mu
   if ((add != SPAMD_SEMIRING_MIN && add != SPAMD_SEMIRING_MAX) || (mul != SPAMD_SEMIRING_PLUS && mul != SPAMD_SEMIRING_TIMES))
     return SPAMD_EINVAL;
   if (M < 0 || K < 0 || N < 0 || nnz < 0 || max_len < 0 || max_len > nnz) return SPAMD_EINVAL;
-  if (group != 8 && group != 16 && group != 32 && group != 64) return SPAMD_EINVAL;
-  if (chunk < 64 || chunk > SR_MAX_CHUNK || chunk % 64) return SPAMD_EINVAL;
+  if (!seg_params_ok(group, chunk, SR_MAX_CHUNK, 0)) return SPAMD_EINVAL;
   if (ldb < N || ldo < N || (init && ldi < N) || (arg && lda < N)) return SPAMD_EINVAL;
   if (M == 0 || N == 0) return 0;
   if (!a_ptr || !out || (nnz > 0 && (!a_idx || !a_val || !b || K == 0))) return SPAMD_EINVAL;

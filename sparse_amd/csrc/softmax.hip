@@ -22,39 +22,15 @@
 //   wide   short_max < n <= chunk: a wave owns the group, 16 registers per lane hold it (chunk <= 1024).  Waves find their
 //          groups by a ballot over 64 segment lengths.  One read, one write.
 //   long   n > chunk: pieces of `chunk` elements, one wave each.  Wave g looks at the plan positions [g * chunk, (g + 1) *
-//          chunk): at most two pieces of long groups START there (csrc/mttkrp.hip has the argument) - workspace slots 2g and
+//          chunk): at most two pieces of long groups START there (csrc/segment_walk.h has the argument) - workspace slots 2g and
 //          2g + 1.  Five launches that each END before the next reads what it wrote - no workgroup waits for another:
 //          piece maxima, group maxima, piece sums, group sums (sequential, piece order), outputs.  Three reads, one write.
-#include "common.h"
+#include "attention_common.h"
 #include "exp_det.h"
-
-#include <algorithm>
-#include <limits>
 
 #define SOFTMAX_MAX_CHUNK 1024
 
 namespace spamd {
-
-template <typename T>
-__device__ __forceinline__ T sm_nmax(T a, T b) {   // NaN wins from either side
-  return (a > b || a != a) ? a : b;
-}
-
-template <typename T, int W>
-__device__ __forceinline__ T sm_xmax(T m) {
-#pragma unroll
-  for (int h = W / 2; h >= 1; h /= 2) m = sm_nmax(m, __shfl_xor(m, h, W));
-  return m;
-}
-
-// a[l] = a[l] + a[l ^ h], h = W / 2 .. 1: every lane ends with the bits of the halving fold (the sum of two is commutative)
-template <typename T, int W>
-__device__ __forceinline__ T sm_xsum(T s) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int h = W / 2; h >= 1; h /= 2) s = s + __shfl_xor(s, h, W);
-  return s;
-}
 
 template <typename T>
 struct SmIn {
@@ -70,11 +46,6 @@ struct SmIn {
   }
 };
 
-template <typename T>
-__device__ __forceinline__ T sm_neg_inf() {
-  return -std::numeric_limits<T>::infinity();
-}
-
 // ---- short: a sub-group of G lanes per group ------------------------------------------------------------------------------
 template <typename T, typename I, int G>
 __global__ void __launch_bounds__(256)
@@ -89,19 +60,19 @@ sm_short_kernel(SmIn<T> in, int64_t nseg, const I* __restrict__ segptr, int64_t 
     if (n < 1 || n > short_max) continue;   // (the same in every lane of the sub-group)
     T t[V];
     int64_t p[V];
-    T m = sm_neg_inf<T>();
+    T m = at_neg_inf<T>();
 #pragma unroll
     for (int j = 0; j < V; ++j) {
       const int q = sub + j * G;
       p[j] = 0;
-      t[j] = sm_neg_inf<T>();
+      t[j] = at_neg_inf<T>();
       if (q < n) {
         p[j] = in.pos(b + q);
         t[j] = in.at(p[j]);
-        m = sm_nmax(m, t[j]);
+        m = at_nmax(m, t[j]);
       }
     }
-    m = sm_xmax<T, G>(m);
+    m = at_xmax<T, G>(m);
     T a[V];
 #pragma unroll
     for (int j = 0; j < V; ++j) {
@@ -112,7 +83,7 @@ sm_short_kernel(SmIn<T> in, int64_t nseg, const I* __restrict__ segptr, int64_t 
     for (int hv = V / 2; hv >= 1; hv /= 2)   // h = 32 .. G: both accumulators live in this lane
 #pragma unroll
       for (int j = 0; j < hv; ++j) a[j] = a[j] + a[j + hv];
-    const T s = sm_xsum<T, G>(a[0]);
+    const T s = at_xsum<T, G>(a[0]);
 #pragma unroll
     for (int j = 0; j < V; ++j)
       if (sub + j * G < n) out[p[j]] = t[j] / s;
@@ -126,19 +97,19 @@ __device__ __forceinline__ void sm_wave_group(const SmIn<T>& in, int64_t b, int6
   constexpr int V = SOFTMAX_MAX_CHUNK / 64;
   T t[V];
   int64_t p[V];
-  T m = sm_neg_inf<T>();
+  T m = at_neg_inf<T>();
 #pragma unroll
   for (int j = 0; j < V; ++j) {
     const int q = lane + j * 64;
     p[j] = 0;
-    t[j] = sm_neg_inf<T>();
+    t[j] = at_neg_inf<T>();
     if (q < n) {
       p[j] = in.pos(b + q);
       t[j] = in.at(p[j]);
-      m = sm_nmax(m, t[j]);
+      m = at_nmax(m, t[j]);
     }
   }
-  m = sm_xmax<T, 64>(m);
+  m = at_xmax<T, 64>(m);
   T acc = T(0);
 #pragma unroll
   for (int j = 0; j < V; ++j) {
@@ -147,7 +118,7 @@ __device__ __forceinline__ void sm_wave_group(const SmIn<T>& in, int64_t b, int6
       acc = acc + t[j];
     }
   }
-  const T s = sm_xsum<T, 64>(acc);
+  const T s = at_xsum<T, 64>(acc);
 #pragma unroll
   for (int j = 0; j < V; ++j)
     if (lane + j * 64 < n) out[p[j]] = t[j] / s;
@@ -158,57 +129,29 @@ __global__ void __launch_bounds__(256)
 sm_wide_kernel(SmIn<T> in, int64_t nseg, const I* __restrict__ segptr, int64_t above, int64_t upto, T* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   const int64_t nwaves = (int64_t)gridDim.x * 4;
-  for (int64_t base = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64; base < nseg; base += nwaves * 64) {
-    const int64_t seg = base + lane;
-    int64_t b = 0, n = 0;
-    if (seg < nseg) {
-      b = (int64_t)segptr[seg];
-      n = (int64_t)segptr[seg + 1] - b;
-    }
-    unsigned long long todo = __ballot(n > above && n <= upto);
-    while (todo) {   // wave-uniform: all 64 lanes stay together
-      const int src = __builtin_ctzll(todo);
-      todo &= todo - 1;
-      sm_wave_group<T>(in, wave_bcast(b, src), wave_bcast(n, src), lane, out);
-    }
-  }
+  for (int64_t base = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64; base < nseg; base += nwaves * 64)
+    seg_wave_each(segptr, nseg, base, lane, [&](int64_t n) { return n > above && n <= upto; },
+                  [&](int, int64_t b, int64_t n) { sm_wave_group<T>(in, b, n, lane, out); });
 }
 
 // ---- long: pieces ------------------------------------------------------------------------------------------------------------
-// last r in [0, nseg] with segptr[r] <= pos (segptr[0] = 0 <= pos): the non-empty segment that holds pos when pos < nnz
-template <typename I>
-__device__ __forceinline__ int64_t sm_seg_of(const I* __restrict__ segptr, int64_t nseg, int64_t pos) {
-  int64_t lo = 0, hi = nseg;
-  while (lo < hi) {
-    const int64_t mid = lo + (hi - lo + 1) / 2;
-    if ((int64_t)segptr[mid] <= pos) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
-// the workspace slot of the piece of a long group (first position b) that starts at position s
-__device__ __forceinline__ int64_t sm_slot(int64_t b, int64_t s, int64_t chunk) {
-  return 2 * (s / chunk) + (s == b && b % chunk != 0 ? 1 : 0);
-}
-
 // workspace: four arrays of 2 * nwin values - piece maxima, piece sums, group maxima and group sums (the last two at the
 // slot of the group's first piece)
 template <typename T, int PHASE>
 __device__ __forceinline__ void sm_piece(const SmIn<T>& in, int64_t b, int64_t s, int64_t e, int64_t chunk, int64_t nwin,
                                          int lane, T* __restrict__ ws, T* __restrict__ out) {
 #pragma clang fp contract(off)
-  const int64_t slot = sm_slot(b, s, chunk), slot0 = sm_slot(b, b, chunk);
+  const int64_t slot = seg_slot(b, s, chunk), slot0 = seg_slot(b, b, chunk);
   if (PHASE == 0) {
-    T m = sm_neg_inf<T>();
-    for (int64_t q = s + lane; q < e; q += 64) m = sm_nmax(m, in.at(in.pos(q)));
-    m = sm_xmax<T, 64>(m);
+    T m = at_neg_inf<T>();
+    for (int64_t q = s + lane; q < e; q += 64) m = at_nmax(m, in.at(in.pos(q)));
+    m = at_xmax<T, 64>(m);
     if (lane == 0) ws[slot] = m;
   } else if (PHASE == 1) {
     const T m = ws[4 * nwin + slot0];
     T acc = T(0);
     for (int64_t q = s + lane; q < e; q += 64) acc = acc + exp_det(in.at(in.pos(q)) - m);
-    acc = sm_xsum<T, 64>(acc);
+    acc = at_xsum<T, 64>(acc);
     if (lane == 0) ws[2 * nwin + slot] = acc;
   } else {
     const T m = ws[4 * nwin + slot0], sum = ws[6 * nwin + slot0];
@@ -224,23 +167,10 @@ __global__ void __launch_bounds__(256)
 sm_piece_kernel(SmIn<T> in, int64_t nnz, int64_t nseg, const I* __restrict__ segptr, int64_t chunk, int64_t nwin,
                 T* __restrict__ ws, T* __restrict__ out) {
   const int lane = threadIdx.x & 63;
-  for (int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); g < nwin; g += (int64_t)gridDim.x * 4) {
-    const int64_t lo = g * chunk;
-    const int64_t hi = lo + chunk < nnz ? lo + chunk : nnz;
-    const int64_t r0 = sm_seg_of(segptr, nseg, lo);   // lo < nnz: r0 < nseg and the segment is not empty
-    {
-      const int64_t b0 = (int64_t)segptr[r0], e0 = (int64_t)segptr[r0 + 1];
-      if (e0 - b0 > chunk) {
-        const int64_t s = b0 + (lo - b0 + chunk - 1) / chunk * chunk;   // the one piece start of this group in [lo, lo + chunk)
-        if (s < hi && s < e0) sm_piece<T, PHASE>(in, b0, s, s + chunk < e0 ? s + chunk : e0, chunk, nwin, lane, ws, out);
-      }
-    }
-    const int64_t r1 = sm_seg_of(segptr, nseg, hi - 1);
-    if (r1 > r0) {   // starts inside the window; only the last such group can be longer than the window
-      const int64_t b1 = (int64_t)segptr[r1], e1 = (int64_t)segptr[r1 + 1];
-      if (e1 - b1 > chunk) sm_piece<T, PHASE>(in, b1, b1, b1 + chunk, chunk, nwin, lane, ws, out);
-    }
-  }
+  for (int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); g < nwin; g += (int64_t)gridDim.x * 4)
+    seg_window_pieces(segptr, nseg, nnz, chunk, g, [&](int64_t, int64_t b, int64_t s, int64_t e) {
+      sm_piece<T, PHASE>(in, b, s, e, chunk, nwin, lane, ws, out);
+    });
 }
 
 // PHASE 0: group maxima from the piece maxima; PHASE 1: group sums, the piece sums added one after the other in piece order
@@ -250,43 +180,20 @@ sm_join_kernel(int64_t nseg, const I* __restrict__ segptr, int64_t chunk, int64_
 #pragma clang fp contract(off)
   const int lane = threadIdx.x & 63;
   const int64_t nwaves = (int64_t)gridDim.x * 4;
-  for (int64_t base = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64; base < nseg; base += nwaves * 64) {
-    const int64_t seg = base + lane;
-    int64_t mb = 0, mn = 0;
-    if (seg < nseg) {
-      mb = (int64_t)segptr[seg];
-      mn = (int64_t)segptr[seg + 1] - mb;
-    }
-    unsigned long long todo = __ballot(mn > chunk);
-    while (todo) {
-      const int src = __builtin_ctzll(todo);
-      todo &= todo - 1;
-      const int64_t b = wave_bcast(mb, src), n = wave_bcast(mn, src);
+  for (int64_t base = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64; base < nseg; base += nwaves * 64)
+    seg_wave_each(segptr, nseg, base, lane, [&](int64_t n) { return n > chunk; }, [&](int, int64_t b, int64_t n) {
       const int64_t np = (n + chunk - 1) / chunk;
-      const int64_t slot0 = sm_slot(b, b, chunk);
+      const int64_t slot0 = seg_slot(b, b, chunk);
       if (PHASE == 0) {
-        T m = sm_neg_inf<T>();
-        for (int64_t k = lane; k < np; k += 64) m = sm_nmax(m, ws[sm_slot(b, b + k * chunk, chunk)]);
-        m = sm_xmax<T, 64>(m);
+        T m = at_neg_inf<T>();
+        for (int64_t k = lane; k < np; k += 64) m = at_nmax(m, ws[seg_slot(b, b + k * chunk, chunk)]);
+        m = at_xmax<T, 64>(m);
         if (lane == 0) ws[4 * nwin + slot0] = m;
       } else {
-        T s = T(0);
-        for (int64_t k0 = 0; k0 < np; k0 += 64) {
-          const int cnt = (int)(np - k0 < 64 ? np - k0 : 64);
-          const T v = lane < cnt ? ws[2 * nwin + sm_slot(b, b + (k0 + lane) * chunk, chunk)] : T(0);
-          for (int u = 0; u < cnt; ++u) {
-            const T pv = wave_bcast(v, u);
-            s = (k0 + u == 0) ? pv : s + pv;
-          }
-        }
+        const T s = seg_join_sum<T>(np, lane, [&](int64_t k) { return ws[2 * nwin + seg_slot(b, b + k * chunk, chunk)]; });
         if (lane == 0) ws[6 * nwin + slot0] = s;
       }
-    }
-  }
-}
-
-static unsigned sm_grid(int64_t items, int64_t per_block) {
-  return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(items, per_block), (int64_t)1 << 20));
+    });
 }
 
 template <typename T, typename I>
@@ -297,34 +204,19 @@ static int softmax_typed(int64_t nseg, int64_t nnz, const void* segptr_, const i
   T* ws = (T*)ws_;
   T* out = (T*)out_;
   SmIn<T> in{(const T*)x, perm, (T)scale, has_scale != 0};
-  if (short_max > 0) {
-#define SM_SHORT(G)                                                                                                     \
-  hipLaunchKernelGGL((sm_short_kernel<T, I, G>), dim3(sm_grid(nseg, 256 / G)), dim3(256), 0, st, in, nseg, segptr, \
-                     short_max, out)
-    if (group == 8) SM_SHORT(8);
-    else if (group == 16) SM_SHORT(16);
-    else if (group == 32) SM_SHORT(32);
-    else SM_SHORT(64);
-#undef SM_SHORT
-    if (int rc = launch_status()) return rc;
-  }
-  if (std::min(max_len, chunk) > short_max) {
-    hipLaunchKernelGGL((sm_wide_kernel<T, I>), dim3(sm_grid(nseg, 256)), dim3(256), 0, st, in, nseg, segptr, short_max, chunk, out);
-    if (int rc = launch_status()) return rc;
-  }
+  const dim3 wg(256);
+  if (short_max > 0)
+    SEG_GROUP(group, G, SPAMD_LAUNCH((sm_short_kernel<T, I, G>), dim3(seg_grid(nseg, 256 / G)), wg, 0, st, in, nseg, segptr, short_max, out));
+  if (std::min(max_len, chunk) > short_max)
+    SPAMD_LAUNCH((sm_wide_kernel<T, I>), dim3(seg_grid(nseg, 256)), wg, 0, st, in, nseg, segptr, short_max, chunk, out);
   if (max_len > chunk) {
     const int64_t nwin = ceil_div(nnz, chunk);
-    const dim3 pg(sm_grid(nwin, 4)), jg(sm_grid(nseg, 256));
-    hipLaunchKernelGGL((sm_piece_kernel<T, I, 0>), pg, dim3(256), 0, st, in, nnz, nseg, segptr, chunk, nwin, ws, out);
-    if (int rc = launch_status()) return rc;
-    hipLaunchKernelGGL((sm_join_kernel<T, I, 0>), jg, dim3(256), 0, st, nseg, segptr, chunk, nwin, ws);
-    if (int rc = launch_status()) return rc;
-    hipLaunchKernelGGL((sm_piece_kernel<T, I, 1>), pg, dim3(256), 0, st, in, nnz, nseg, segptr, chunk, nwin, ws, out);
-    if (int rc = launch_status()) return rc;
-    hipLaunchKernelGGL((sm_join_kernel<T, I, 1>), jg, dim3(256), 0, st, nseg, segptr, chunk, nwin, ws);
-    if (int rc = launch_status()) return rc;
-    hipLaunchKernelGGL((sm_piece_kernel<T, I, 2>), pg, dim3(256), 0, st, in, nnz, nseg, segptr, chunk, nwin, ws, out);
-    if (int rc = launch_status()) return rc;
+    const dim3 pg(seg_grid(nwin, 4)), jg(seg_grid(nseg, 256));
+    SPAMD_LAUNCH((sm_piece_kernel<T, I, 0>), pg, wg, 0, st, in, nnz, nseg, segptr, chunk, nwin, ws, out);
+    SPAMD_LAUNCH((sm_join_kernel<T, I, 0>), jg, wg, 0, st, nseg, segptr, chunk, nwin, ws);
+    SPAMD_LAUNCH((sm_piece_kernel<T, I, 1>), pg, wg, 0, st, in, nnz, nseg, segptr, chunk, nwin, ws, out);
+    SPAMD_LAUNCH((sm_join_kernel<T, I, 1>), jg, wg, 0, st, nseg, segptr, chunk, nwin, ws);
+    SPAMD_LAUNCH((sm_piece_kernel<T, I, 2>), pg, wg, 0, st, in, nnz, nseg, segptr, chunk, nwin, ws, out);
   }
   return 0;
 }
@@ -336,7 +228,7 @@ using namespace spamd;
 extern "C" int64_t spamd_softmax_ws_bytes(int val_dtype, int64_t nnz, int64_t chunk) {
   const int64_t esz = val_dtype == SPAMD_F32 ? 4 : (val_dtype == SPAMD_F64 ? 8 : 0);
   if (!esz) return SPAMD_ETYPE;
-  if (nnz < 0 || chunk < 64 || chunk > SOFTMAX_MAX_CHUNK || chunk % 64) return SPAMD_EINVAL;
+  if (nnz < 0 || !seg_chunk_ok(chunk, SOFTMAX_MAX_CHUNK)) return SPAMD_EINVAL;
   if (nnz <= chunk) return 0;
   return 8 * ceil_div(nnz, chunk) * esz;
 }
@@ -347,8 +239,7 @@ extern "C" int spamd_softmax(int val_dtype, int idx_dtype, int64_t nseg, int64_t
   if (val_dtype != SPAMD_F32 && val_dtype != SPAMD_F64) return SPAMD_ETYPE;
   if (idx_dtype != SPAMD_I32 && idx_dtype != SPAMD_I64) return SPAMD_ETYPE;
   if (nseg < 0 || nnz < 0 || max_len < 0 || max_len > nnz) return SPAMD_EINVAL;
-  if (group != 8 && group != 16 && group != 32 && group != 64) return SPAMD_EINVAL;
-  if (chunk < 64 || chunk > SOFTMAX_MAX_CHUNK || chunk % 64 || short_max < 0 || short_max > 64) return SPAMD_EINVAL;
+  if (!seg_params_ok(group, chunk, SOFTMAX_MAX_CHUNK, short_max)) return SPAMD_EINVAL;
   if (nseg == 0 || nnz == 0 || max_len == 0) return 0;
   if (!segptr || !x || !out || out == x) return SPAMD_EINVAL;
   if (max_len > chunk && (!ws || ws_bytes < spamd_softmax_ws_bytes(val_dtype, nnz, chunk))) return SPAMD_EWS;

@@ -57,7 +57,7 @@ def _case_names():
     names = [f"width{R}_{idx}" for R in WIDTHS for idx in ("int32", "int64")]
     names += [f"unit_dim_mode{m}" for m in range(4)]
     names += [f"rows_mode{m}_r{R}" for m in (0, 2) for R in (5, 17)]
-    names += ["one_row_chunk8", "one_row_default", "long_row_default_chunk", "bool_values_2d", "int_values_5d"]
+    names += ["one_row_chunk8", "one_row_default", "long_row_default_chunk", "two_starts_chunk64", "bool_values_2d", "int_values_5d"]
     return names
 
 
@@ -85,6 +85,9 @@ def _case(name):
     if name == "long_row_default_chunk":      # 5000 elements in one row: the default chunk's multi-piece path
         coords, data, shape = mc.rows_tensor(500, [3, 5000, 0, 10], (80, 70), 1, np.float32)
         return coords, data, shape, tuple(mc.factors_for(500, shape, 3, np.float32, mode=1)), 1, None, np.float32, np.int32
+    if name == "two_starts_chunk64":      # windows 2 and 3 hold two piece starts each: a long row starts mid-window after another's piece
+        coords, data, shape = mc.rows_tensor(550, [3, 130, 70, 1, 200], (16, 13), 1, np.float64)
+        return coords, data, shape, tuple(mc.factors_for(550, shape, 17, np.float64, mode=1)), 1, 64, np.float64, np.int64
     if name == "bool_values_2d":
         shape = (11, 13)
         coords, data = mc.random_tensor(600, shape, 60, np.bool_)
