@@ -483,7 +483,10 @@ int spamd_transpose_2d(int elem_bytes, int64_t rows, int64_t cols, const void* i
  * parts - the matrix without them and the hot rows cut into pieces that are rows of their own - through the CSR x dense kernels
  * above (reference `_dot_csr_ndarray`, _common.py:720-755: one core walks such a row as one wave does here); this adds the
  * pieces' results into the hot rows of the result: out[rows[h], :] = sum over v in [vfirst[h], vfirst[h + 1]) of part[v, :],
- * in piece order.  val_dtype F32 | F64 | I32 | I64; vfirst has n_hot + 1 entries. */
+ * in piece order.  val_dtype F32 | F64 | I32 | I64; vfirst has n_hot + 1 entries.  The sum starts from T(0) and adds the pieces
+ * one after the other in the result type (integers wrap around); a hot row without pieces (vfirst[h] == vfirst[h + 1]) has its
+ * row of `out` set to zero.  Rows of `out` that `rows` does not name and the columns from n_cols on (ld_part, ld_out >= n_cols)
+ * are neither read nor written. */
 int spamd_hot_rows_combine(int val_dtype, int64_t n_hot, int64_t n_cols, const void* part, int64_t ld_part,
                            const int64_t* vfirst, const int64_t* rows, void* out, int64_t ld_out, void* stream);
 

@@ -7,7 +7,10 @@ stride test for a slice); the masks are AND-ed, the survivors compacted, and the
 integer arithmetic — all through the elementwise/compaction kernels of libsparse_amd.so.  An integer array index
 (`take`) is a join of the survivors' coordinates with the index array: the array is sorted once, two binary searches per
 stored element give the run of positions that ask for its coordinate, and the element is replicated that often
-(scan + expansion).  Several array indices at once are not on this path and raise NotImplementedError."""
+(scan + expansion).  The array index's axis stands in the array's place, as in the reference (`_coo/indexing.py:83-103`) - also
+where NumPy, which counts an integer as an advanced index too, moves it to the front: with an integer BEFORE the array and a
+slice or `None` between them, `x[2, :, [5, 5, 1]]` of a (5, 6, 7) array is (6, 3) here and in the reference, (3, 6) in NumPy.
+Several array indices at once are not on this path and raise NotImplementedError."""
 import numpy as np
 import torch
 
