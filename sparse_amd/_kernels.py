@@ -6,6 +6,7 @@ entry point of libsparse_amd.so (a few for the composite kernels) on the current
 path (products, sums, sorts, scans, merges) happens in that library; torch is used for allocation, views, dtype
 casts of operands and host<->device copies.
 """
+import functools
 import os
 
 import numpy as np
@@ -846,23 +847,76 @@ def dot_ndarray_coo_sparse(a, coords, data, out_shape, as_keys=False, st=None):
 
 SPGEMM_CHUNK_PRODUCTS = 1 << 27  # products expanded/sorted at a time (bounds workspace to ~5 GB)
 SPGEMM_RUN_PROBE_MIN = 1 << 13   # chunks with fewer products: even one output element holding all of them is short work
+SPGEMM_RUN_DUPS_MIN = 1023       # ... and with fewer products that share their element with an earlier one there is no long run
 SPGEMM_RUN_LONG = True           # False: always the one-thread-per-element sums (tests)
 
 
-def _spgemm_keys(n_row, n_col, a_data, a_indices, a_rows, b_data, b_indices, b_indptr):
+@functools.lru_cache(maxsize=None)
+def _spgemm_vcode(dtr):
+    """`code_of` the result type, None where it raises: complex values, which only the global form takes, and the types no
+    kernel takes (the global form's `product_code` raises for those).  (Remembered: the route and the operands both ask.)"""
+    try:
+        return code_of(dtr)
+    except TypeError:
+        return None
+
+
+class SpgemmOperands:
+    """The operands of one sparse @ sparse product, prepared once (`_spgemm_operands`) and handed to every executor: the
+    shape, the result type `dtr` with its value code (`_spgemm_vcode`), both value arrays cast to `dtr`, the index arrays
+    contiguous and of one width `it`, the device and its stream.  The width is unified over four arrays for the small, bitmap and bucket
+    kernels; `keys_index` = (a_indices, b_indices, b_indptr, their type) is the global form's width over those three alone (a
+    GCXS may have int32 indices and int64 pointers: the same tensors wherever the two widths agree).  `a_rows`: the row id
+    of every element of A where the caller has it (COO), else None (`_spgemm_a_rows`)."""
+
+    __slots__ = ("n_row", "n_inner", "n_col", "dtr", "vcode", "it", "a_data", "a_indices", "a_indptr", "b_data", "b_indices",
+                 "b_indptr", "keys_index", "a_rows", "dev", "s")
+
+
+def _spgemm_operands(n_row, n_col, dtr, a_data, a_indices, a_indptr, b_data, b_indices, b_indptr, a_rows=None, row_local=True):
+    """SpgemmOperands of a product; `row_local` False: for the global form alone (A's pointers stay as they are, out of the
+    index width)."""
+    p = SpgemmOperands()
+    p.n_row, p.n_inner, p.n_col, p.dtr = n_row, int(b_indptr.numel()) - 1, n_col, dtr
+    p.dev = require_hip(a_data, b_data)
+    p.s, p.vcode = stream_ptr(p.dev), _spgemm_vcode(dtr)
+    p.a_data = a_data.to(dtr).contiguous() if a_data.dtype != dtr else a_data.contiguous()
+    p.b_data = b_data.to(dtr).contiguous() if b_data.dtype != dtr else b_data.contiguous()
+    a_indices, b_indices, b_indptr = a_indices.contiguous(), b_indices.contiguous(), b_indptr.contiguous()
+    if not row_local:
+        (p.a_indices, p.b_indices, p.b_indptr), p.it = _unify_index(a_indices, b_indices, b_indptr)
+        p.a_indptr, p.keys_index = a_indptr, (p.a_indices, p.b_indices, p.b_indptr, p.it)
+    else:
+        (p.a_indices, p.a_indptr, p.b_indices, p.b_indptr), p.it = _unify_index(a_indices, a_indptr.contiguous(), b_indices, b_indptr)
+        if p.it == torch.int64 and a_indices.dtype == b_indices.dtype == b_indptr.dtype == torch.int32:
+            p.keys_index = (a_indices, b_indices, b_indptr, torch.int32)    # (A's pointers alone are wide)
+        else:
+            p.keys_index = (p.a_indices, p.b_indices, p.b_indptr, p.it)
+    p.a_rows = a_rows
+    return p
+
+
+def _spgemm_a_rows(p):
+    """The row id of every element of A (int64): the caller's, else from A's pointers.  One product asks once: the global
+    form for all of A, or the bucket path for its heavy rows."""
+    if p.a_rows is not None:
+        return convert(p.a_rows.contiguous(), torch.int64)
+    return csr_to_keys(p.a_indptr, torch.zeros_like(p.a_indices, dtype=p.a_indptr.dtype), p.n_row, 1)
+
+
+def _spgemm_keys(p, part=None):
     """Expand-sort-compress over row chunks; returns (keys, data) sorted by row*n_col + col with
-    every output element summed in the reference's order."""
+    every output element summed in the reference's order.  `part` = (a_data, a_indices, a_rows) of the elements of A to
+    take, at the width of `p.it` (the heavy rows of the bucket path); None: all of A, at the width of `p.keys_index`."""
     from ._reduce import segment_reduce
 
-    dev = require_hip(a_data, b_data)
-    dtr = torch_dtype(dot_dtype(a_data.dtype, b_data.dtype))
+    n_row, n_col, dtr, dev, s = p.n_row, p.n_col, p.dtr, p.dev, p.s
     vcode = product_code(dtr)
-    a_data = a_data.to(dtr).contiguous() if a_data.dtype != dtr else a_data.contiguous()
-    b_data = b_data.to(dtr).contiguous() if b_data.dtype != dtr else b_data.contiguous()
-    (a_indices, b_indices, b_indptr), it = _unify_index(a_indices.contiguous(), b_indices.contiguous(),
-                                                        b_indptr.contiguous())
+    if part is None:
+        a_data, a_rows, b_data, (a_indices, b_indices, b_indptr, it) = p.a_data, _spgemm_a_rows(p), p.b_data, p.keys_index
+    else:
+        (a_data, a_indices, a_rows), b_data, b_indices, b_indptr, it = part, p.b_data, p.b_indices, p.b_indptr, p.it
     nnz_a = int(a_indices.numel())
-    s = stream_ptr(dev)
     out_keys, out_vals = [], []
     if nnz_a == 0:
         return torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=dtr, device=dev)
@@ -900,7 +954,7 @@ def _spgemm_keys(n_row, n_col, a_data, a_indices, a_rows, b_data, b_indices, b_i
             ho = exclusive_scan(heads)
             c = int(ho[-1])
             summed = None
-            if P >= SPGEMM_RUN_PROBE_MIN and P - c >= 1023 and dtr in _CODE_T and dtr != torch.bool:
+            if P >= SPGEMM_RUN_PROBE_MIN and P - c >= SPGEMM_RUN_DUPS_MIN and dtr in _CODE_T and dtr != torch.bool:
                 # one thread per output element adds its products left to right (the reference's `sums[j] += ...` order, bit for
                 # bit) - and walks alone when an element has 5 x 10^4 of them (the diagonal element of a hub row in a @ a.T:
                 # 10.5 ms of a 15 ms product, tools/r06/spgemm_hub.py).  When the scan of the head flags shows a window of 1024
@@ -922,7 +976,7 @@ def _spgemm_keys(n_row, n_col, a_data, a_indices, a_rows, b_data, b_indices, b_i
 SPGEMM_ROW_LOCAL = True  # tuning hook: False = always the global expand-sort-compress
 
 
-SPGEMM_STATS = {}   # last row-local product: rows, rows left to the global form (diagnostics for the benches)
+SPGEMM_STATS = {}   # last product: its route, rows, rows left to the global form (diagnostics for the benches; `_spgemm` writes it)
 SPGEMM_BITMAP = True            # wide rows of a matrix with <= 2^20 columns: csrc/spgemm_bitmap.hip (rows written in place)
 SPGEMM_BITMAP_MIN_MEAN = 1300   # mean products per row from which the per-row bitmap scan (n_col / 8 bytes of LDS) pays: measured
 #                                 at n_col = 10^6, 60000 rows (tools/r04/spgemm_sweep.py; ms buckets / bitmap), round 6 (the bitmap
@@ -936,23 +990,24 @@ _BITMAP_UNSUPPORTED = set()    # (device index, split form?) whose launch the li
 _BITMAP_REFUSAL_CODES = (1, 2, 9, 701)   # hipError_t values that mean "not with these resources", not "the device faulted"
 
 
-def _spgemm_bitmap(vcode, it, n_row, n_inner, n_col, parts, total, a_indptr, a_indices, a_data, b_indptr, b_indices, b_data, dtr,
-                   dev, s):
-    """C = A @ B by csrc/spgemm_bitmap.hip: (data, int64 indices, int64 indptr), or None when a row (or part of a row)
-    exceeded the kernel's limits (the caller then tries the next form).  `parts` = 1: whole rows, one workgroup per CU;
-    > 1: column ranges, two workgroups per CU.  The result buffers are allocated for every product (an upper bound of the
-    result's length) and trimmed: a view when at least 3/4 of them are used."""
+def _spgemm_bitmap(p, parts, total):
+    """C = A @ B by csrc/spgemm_bitmap.hip: ((data, int64 indices, int64 indptr), seen), the triple None when a row (or part
+    of a row) exceeded the kernel's limits or the library refuses this form on this device (the caller then tries the next
+    form); `seen` = what the attempt leaves for SPGEMM_STATS.  `parts` = 1: whole rows, one workgroup per CU; > 1: column
+    ranges, two workgroups per CU.  The result buffers are allocated for every product (an upper bound of the result's
+    length) and trimmed: a view when at least 3/4 of them are used."""
+    n_row, dev = p.n_row, p.dev
+    if (dev.index, parts > 1) in _BITMAP_UNSUPPORTED:
+        return None, {}
     out_idx = torch.empty(max(total, 1), dtype=torch.int64, device=dev)
-    out_val = torch.empty(max(total, 1), dtype=dtr, device=dev)
+    out_val = torch.empty(max(total, 1), dtype=p.dtr, device=dev)
     out_ptr = torch.empty(n_row + 1, dtype=torch.int64, device=dev)
     work = torch.empty(n_row * parts + 32, dtype=torch.int64, device=dev)
-    bsplit = torch.empty(max(n_inner * (parts - 1), 1), dtype=it, device=dev) if parts > 1 else None
-    if (dev.index, parts > 1) in _BITMAP_UNSUPPORTED:
-        return None
+    bsplit = torch.empty(max(p.n_inner * (parts - 1), 1), dtype=p.it, device=dev) if parts > 1 else None
     try:
-        _ffi.call("spamd_spgemm_bitmap", vcode, code_of(it), n_row, n_inner, n_col, parts, ptr(a_indptr), ptr(a_indices), ptr(a_data),
-                  ptr(b_indptr), ptr(b_indices), ptr(b_data), ptr(bsplit) if bsplit is not None else None, ptr(work), ptr(out_ptr),
-                  ptr(out_idx), ptr(out_val), s)
+        _ffi.call("spamd_spgemm_bitmap", p.vcode, code_of(p.it), n_row, p.n_inner, p.n_col, parts, ptr(p.a_indptr), ptr(p.a_indices),
+                  ptr(p.a_data), ptr(p.b_indptr), ptr(p.b_indices), ptr(p.b_data), ptr(bsplit) if bsplit is not None else None,
+                  ptr(work), ptr(out_ptr), ptr(out_idx), ptr(out_val), p.s)
     except _ffi.HipBackendError as e:
         # the launch itself was REFUSED - a negative SPAMD_E* from the range / LDS checks, or the runtime declining the 160 KB
         # LDS opt-in or the occupancy query on a part with less (hipErrorInvalidValue 1, hipErrorOutOfMemory 2,
@@ -963,22 +1018,20 @@ def _spgemm_bitmap(vcode, it, n_row, n_inner, n_col, parts, total, a_indptr, a_i
         if code > 0 and code not in _BITMAP_REFUSAL_CODES:
             raise
         _BITMAP_UNSUPPORTED.add((dev.index, parts > 1))
-        SPGEMM_STATS["bitmap_refused"] = SPGEMM_STATS.get("bitmap_refused", 0) + 1
-        return None
+        return None, {"bitmap_refused": 1}
     failed, zeros, nnz = (int(v) for v in torch.cat([work[1:3], out_ptr[-1:]]).tolist())   # ONE read-back
+    seen = {}
     if os.environ.get("SPAMD_BMK_PROF"):     # (-DBMK_PROF builds of csrc/spgemm_bitmap.hip: cycles per phase, thread 0 of every workgroup)
-        SPGEMM_STATS["phase_cycles"] = work[4:20].tolist()
+        seen["phase_cycles"] = work[4:20].tolist()
     if failed:
-        SPGEMM_STATS["bitmap_failed"] = SPGEMM_STATS.get("bitmap_failed", 0) + 1
-        return None
+        seen["bitmap_failed"] = 1
+        return None, seen
     if nnz * 4 < total * 3:
         out_idx, out_val = out_idx[:nnz].clone(), out_val[:nnz].clone()
     else:
         out_idx, out_val = out_idx[:nnz], out_val[:nnz]
     note_zero_bits_count(out_val, zeros)
-    SPGEMM_STATS["rows"], SPGEMM_STATS["heavy_or_declined"], SPGEMM_STATS["kernel"] = n_row, 0, "bitmap"
-    SPGEMM_STATS["parts"] = parts
-    return out_val, out_idx, out_ptr
+    return (out_val, out_idx, out_ptr), seen
 
 
 SPGEMM_BITMAP_SPLIT = True   # tuning hook: False = only the wide form (whole rows, one workgroup per CU); "first" = the split form first
@@ -1032,149 +1085,220 @@ def _spgemm_small_second(vcode, n_row, n_col, total):
     return fill >= 1.0 or (n_col <= four_waves and fill >= 0.25)
 
 
+def _spgemm_small_fits(vcode, n_row, n_col):
+    """Whether csrc/spgemm_small.hip takes a result of this shape at all (a zero-width result: the kernel's argument check
+    refuses n_col <= 0; the general path returns the empty matrix)."""
+    return vcode is not None and n_row != 0 and n_col != 0 and n_col <= int(_ffi.lib().spamd_spgemm_small_max_cols(vcode))
 
 
-def _spgemm_small(n_row, n_col, a_data, a_indices, a_indptr, b_data, b_indices, b_indptr, bound=None):
+def _spgemm_route(n_row, n_col, nnz_a, dtr, products=None):
+    """The one choice of kernel for sparse @ sparse: the steps to try in order, each of which may decline (`_spgemm` then
+    takes the next one) - ("small", bound), ("probe",), ("bitmap", parts), ("buckets",), ("global",) - from plain numbers:
+    the result's shape, the stored elements of A, the result type and, once the row-product probe has run, `products` =
+    (total, max_prod, max_arow).  Pure but for the SPGEMM_* switches, read at the call, and the library's host-only limits.
+
+    Before the probe (`products` None): the first chance of the one-launch kernel where the result and A are small; then
+    ("probe",) when it is worth launching, else ("global",) - the row-local, small and bitmap kernels are real-only (the global
+    expand-sort-compress has complex values, and the TypeError of a type no kernel takes), and they have no rows to walk
+    (`n_row` 0) or no room for the column in their keys (`n_col` >= 2^31 - 1).  After it: the second chance of the small
+    kernel (`_spgemm_small_second`, its buffers bounded by `total`), the forms of the bitmap kernel where the mean row has
+    SPGEMM_BITMAP_MIN_MEAN products and no row of A is longer than the kernel stages (`_spgemm_bitmap_forms`), the bucket
+    kernels, the global form.  What only the device can tell - a `failed` word, a refused launch, mostly heavy rows - is a
+    decline of the executor, not a rule here."""
+    if not SPGEMM_ROW_LOCAL:
+        return (("global",),)
+    vcode = _spgemm_vcode(dtr)
+    if products is None:
+        steps = ()
+        if SPGEMM_SMALL and n_row * n_col <= SPGEMM_SMALL_MAX_CELLS and nnz_a <= SPGEMM_SMALL_MAX_NNZ and _spgemm_small_fits(vcode, n_row, n_col):
+            steps = (("small", None),)
+        return steps + ((("global",),) if vcode is None or n_col >= 2 ** 31 - 1 or n_row == 0 else (("probe",),))
+    total, max_prod, max_arow = products
+    steps = []
+    if _spgemm_small_second(vcode, n_row, n_col, total):
+        steps.append(("small", total))
+    if SPGEMM_BITMAP and total and max_arow <= _ffi.lib().spamd_spgemm_bitmap_limits(vcode, 1) and total >= SPGEMM_BITMAP_MIN_MEAN * n_row:
+        steps += [("bitmap", parts) for parts in _spgemm_bitmap_forms(vcode, n_col, max_prod)]
+    return (*steps, ("buckets",), ("global",))
+
+
+def _spgemm_small_run(p, bound=None):
     """csrc/spgemm_small.hip: the whole product in one launch and one read-back (the reference's own benchmark sizes,
-    benchmarks/test_benchmark_coo.py:9-40, are launch-bound on the general path: 230-300 us against ~70).  None when the
-    operands are outside its limits or B is not canonical (the caller takes the general path)."""
-    dev = require_hip(a_data, b_data)
-    dtr = torch_dtype(dot_dtype(a_data.dtype, b_data.dtype))
-    try:
-        vcode = code_of(dtr)
-    except TypeError:
-        return None
-    if n_row == 0 or n_col == 0 or n_col > int(_ffi.lib().spamd_spgemm_small_max_cols(vcode)):
-        return None     # (a zero-width result: the kernel's argument check refuses n_col <= 0; the general path returns the empty matrix)
-    a_data = a_data.to(dtr).contiguous() if a_data.dtype != dtr else a_data.contiguous()
-    b_data = b_data.to(dtr).contiguous() if b_data.dtype != dtr else b_data.contiguous()
-    (a_indices, a_indptr, b_indices, b_indptr), it = _unify_index(a_indices.contiguous(), a_indptr.contiguous(),
-                                                                  b_indices.contiguous(), b_indptr.contiguous())
+    benchmarks/test_benchmark_coo.py:9-40, are launch-bound on the general path: 230-300 us against ~70).  None when a row
+    is outside its limits or B is not canonical (the caller takes the general path); the shape is the caller's to check
+    (`_spgemm_small_fits`: the route does).
+    `bound`: an upper bound of the result's length below its cells (the products, on the second chance)."""
+    n_row, n_col, dev = p.n_row, p.n_col, p.dev
     cells = n_row * n_col if bound is None else min(n_row * n_col, int(bound))     # (the result holds at most one element per product)
     out_idx = torch.empty(cells, dtype=torch.int64, device=dev)
-    out_val = torch.empty(cells, dtype=dtr, device=dev)
+    out_val = torch.empty(cells, dtype=p.dtr, device=dev)
     head = torch.empty(2 * n_row + 8, dtype=torch.int64, device=dev)      # [work (n_row + 4) | out_indptr (n_row + 1)]: one buffer, one read-back
     work, out_ptr = head[: n_row + 4], head[n_row + 4: 2 * n_row + 5]
-    _ffi.call("spamd_spgemm_small", vcode, code_of(it), n_row, n_col, ptr(a_indptr), ptr(a_indices), ptr(a_data), ptr(b_indptr),
-              ptr(b_indices), ptr(b_data), ptr(work), ptr(out_ptr), ptr(out_idx), ptr(out_val), stream_ptr(dev))
+    _ffi.call("spamd_spgemm_small", p.vcode, code_of(p.it), n_row, n_col, ptr(p.a_indptr), ptr(p.a_indices), ptr(p.a_data),
+              ptr(p.b_indptr), ptr(p.b_indices), ptr(p.b_data), ptr(work), ptr(out_ptr), ptr(out_idx), ptr(out_val), p.s)
     failed, zeros, nnz = read_words(head[1:4])      # ONE read-back (three adjacent words, through pinned host memory)
     if failed:
         return None
     out_idx, out_val = (out_idx[:nnz].clone(), out_val[:nnz].clone()) if nnz * 4 < cells * 3 else (out_idx[:nnz], out_val[:nnz])
     note_zero_bits_count(out_val, zeros)
-    SPGEMM_STATS.update(kernel="small", rows=n_row, heavy_or_declined=0)
     return out_val, out_idx, out_ptr
 
 
-def _spgemm_rows(n_row, n_col, a_data, a_indices, a_indptr, b_data, b_indices, b_indptr):
-    """Row-local SpGEMM (csrc/spgemm_rows.hip): (data, int64 indices, int64 indptr) of A @ B.  Rows too heavy for LDS
-    are computed by the global expand-sort-compress and merged in; None when most of the work is in such rows (the
-    caller then uses the global form throughout)."""
-    if SPGEMM_SMALL and n_row * n_col <= SPGEMM_SMALL_MAX_CELLS and int(a_data.numel()) <= SPGEMM_SMALL_MAX_NNZ:
-        res = _spgemm_small(n_row, n_col, a_data, a_indices, a_indptr, b_data, b_indices, b_indptr)
-        if res is not None:
-            return res
-    dev = require_hip(a_data, b_data)
-    dtr = torch_dtype(dot_dtype(a_data.dtype, b_data.dtype))
-    if dtr.is_complex:
-        return None     # the row-local, small and bitmap kernels are real-only: the global expand-sort-compress has complex values
-    vcode = code_of(dtr)
-    if n_col >= 2 ** 31 - 1 or n_row == 0:
-        return None
-    a_data = a_data.to(dtr).contiguous() if a_data.dtype != dtr else a_data.contiguous()
-    b_data = b_data.to(dtr).contiguous() if b_data.dtype != dtr else b_data.contiguous()
-    (a_indices, a_indptr, b_indices, b_indptr), it = _unify_index(a_indices.contiguous(), a_indptr.contiguous(),
-                                                                  b_indices.contiguous(), b_indptr.contiguous())
-    s = stream_ptr(dev)
-    prod = torch.empty(n_row + 1, dtype=torch.int64, device=dev)
-    maxes = torch.empty(2, dtype=torch.int64, device=dev)
-    _ffi.call("spamd_spgemm_row_products", code_of(it), n_row, ptr(a_indptr), ptr(a_indices), ptr(b_indptr), ptr(prod),
-              ptr(maxes), s)
+def _spgemm_probe(p):
+    """The products of every output row (csrc/spgemm_rows.hip): (prod[n_row + 1], their exclusive scan, total, max_prod,
+    max_arow) - one launch, one scan, the two maxima through pinned memory and the total."""
+    prod = torch.empty(p.n_row + 1, dtype=torch.int64, device=p.dev)
+    maxes = torch.empty(2, dtype=torch.int64, device=p.dev)
+    _ffi.call("spamd_spgemm_row_products", code_of(p.it), p.n_row, ptr(p.a_indptr), ptr(p.a_indices), ptr(p.b_indptr), ptr(prod),
+              ptr(maxes), p.s)
     prod_off = exclusive_scan(prod)
-    max_prod, max_arow = read_words(maxes) if maxes.dtype == torch.int64 else (int(v) for v in maxes.tolist())
-    cap = int(_ffi.lib().spamd_spgemm_rows_capacity(vcode, n_col, max_arow))
-    total = int(prod_off[-1])
-    lim = _ffi.lib().spamd_spgemm_bitmap_limits
-    SPGEMM_STATS.update(max_prod=max_prod, max_arow=max_arow, products=total)
-    SPGEMM_STATS.pop("bitmap_failed", None)
-    if _spgemm_small_second(vcode, n_row, n_col, total):
-        try:
-            res = _spgemm_small(n_row, n_col, a_data, a_indices, a_indptr, b_data, b_indices, b_indptr, bound=total)
-        except torch.OutOfMemoryError:       # (its buffers hold min(cells, products) entries: the other kernels need less)
-            res = None
-        if res is not None:
-            return res
-    if SPGEMM_BITMAP and total and max_arow <= lim(vcode, 1) and total >= SPGEMM_BITMAP_MIN_MEAN * n_row:
-        n_inner = int(b_indptr.numel()) - 1
-        for parts in _spgemm_bitmap_forms(vcode, n_col, max_prod):
-            res = _spgemm_bitmap(vcode, it, n_row, n_inner, n_col, parts, total, a_indptr, a_indices, a_data, b_indptr, b_indices,
-                                 b_data, dtr, dev, s)
-            if res is not None:
-                return res
-    SPGEMM_STATS["kernel"] = "buckets"
+    max_prod, max_arow = read_words(maxes)
+    return prod, prod_off, int(prod_off[-1]), max_prod, max_arow
 
-    def classify(nnz_row):
-        """(flags[n_row + 1], rows, their products, rows heavy only by their A length) - csrc/spgemm_rows.hip"""
-        flags = new_flags(n_row, dev)
-        counts = torch.empty(3, dtype=torch.int64, device=dev)
-        _ffi.call("spamd_spgemm_classify_rows", code_of(it), n_row, ptr(prod), ptr(a_indptr), ptr(nnz_row) if nnz_row is not None else 0,
-                  cap, ptr(flags), ptr(counts), s)
-        return (flags, *[int(v) for v in counts.tolist()])
 
+def _spgemm_classify(p, prod, cap, nnz_row):
+    """(flags[n_row + 1], rows, their products, rows heavy only by their A length) - csrc/spgemm_rows.hip"""
+    flags = new_flags(p.n_row, p.dev)
+    counts = torch.empty(3, dtype=torch.int64, device=p.dev)
+    _ffi.call("spamd_spgemm_classify_rows", code_of(p.it), p.n_row, ptr(prod), ptr(p.a_indptr), ptr(nnz_row) if nnz_row is not None else 0,
+              cap, ptr(flags), ptr(counts), p.s)
+    return (flags, *[int(v) for v in counts.tolist()])
+
+
+def _spgemm_merge_heavy(p, flags, n_heavy, prod_off, tmp_cols, tmp_vals, nnz_row):
+    """The `n_heavy` rows that `flags` marks, computed by the global form over their elements of A and copied into the
+    bucket kernels' scratch (`tmp_cols` / `tmp_vals` at `prod_off`, their lengths into `nnz_row`)."""
+    dev, s, n_row = p.dev, p.s, p.n_row
+    nA = int(p.a_indices.numel())
+    iota = torch.empty(max(n_row, nA) + 1, dtype=torch.int64, device=dev)
+    _ffi.call("spamd_iota", int(iota.numel()), ptr(iota), s)
+    heavy_rows = compact(iota[:n_row], flags, exclusive_scan(flags), n_heavy)
+    a_rows = _spgemm_a_rows(p)
+    eflags = new_flags(nA, dev)
+    _ffi.call("spamd_gather", 8, nA, ptr(flags), ptr(a_rows), ptr(eflags), s)
+    eflags[nA:] = 0
+    eoff = exclusive_scan(eflags)
+    sel = compact(iota[:nA], eflags, eoff, int(eoff[-1]))               # A elements of those rows
+    hkeys, hvals = _spgemm_keys(p, (gather(p.a_data, sel), gather(p.a_indices, sel), gather(a_rows, sel)))
+    hptr, hidx = keys_to_csr(hkeys, n_row, p.n_col, torch.int64)
+    _ffi.call("spamd_spgemm_unpack", p.vcode, n_heavy, ptr(heavy_rows.contiguous()), ptr(hptr),
+              ptr(hidx), ptr(hvals.contiguous()), ptr(prod_off), ptr(tmp_cols), ptr(tmp_vals), ptr(nnz_row), s)
+
+
+def _spgemm_buckets(p, prod, prod_off, total, max_prod, max_arow):
+    """Row-local SpGEMM (csrc/spgemm_rows.hip): ((data, int64 indices, int64 indptr) of A @ B, the rows it left to the
+    global form).  Rows too heavy for LDS are computed by the global expand-sort-compress and merged in; None when most
+    of the work is in such rows (the caller then uses the global form throughout)."""
+    n_row, dev, s = p.n_row, p.dev, p.s
+    cap = int(_ffi.lib().spamd_spgemm_rows_capacity(p.vcode, p.n_col, max_arow))
     if max_prod > cap or max_arow > cap:
         # rows too heavy for LDS (products, or A elements to stage) go through the global expand-sort-compress
-        _, n_heavy, heavy_products, n_arow_only = classify(None)
+        _, n_heavy, heavy_products, n_arow_only = _spgemm_classify(p, prod, cap, None)
         if n_heavy * 4 > n_row or heavy_products * 4 > total * 3 or n_arow_only:
             return None  # mostly heavy (or rows heavy only by their A length): the global form throughout
     tmp_cols = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
-    tmp_vals = torch.empty(max(total, 1), dtype=dtr, device=dev)
+    tmp_vals = torch.empty(max(total, 1), dtype=p.dtr, device=dev)
     nnz_row = torch.zeros(n_row + 1, dtype=torch.int64, device=dev)
-    _ffi.call("spamd_spgemm_rows", vcode, code_of(it), n_row, n_col, ptr(a_indptr), ptr(a_indices), ptr(a_data),
-              ptr(b_indptr), ptr(b_indices), ptr(b_data), ptr(prod_off), min(max_prod, cap), max_arow, ptr(tmp_cols),
+    _ffi.call("spamd_spgemm_rows", p.vcode, code_of(p.it), n_row, p.n_col, ptr(p.a_indptr), ptr(p.a_indices), ptr(p.a_data),
+              ptr(p.b_indptr), ptr(p.b_indices), ptr(p.b_data), ptr(prod_off), min(max_prod, cap), max_arow, ptr(tmp_cols),
               ptr(tmp_vals), ptr(nnz_row), s)
     # rows above the capacity were skipped, rows with a column of more than 64 products were declined (nnz_row = -1):
     # both are computed by the global form and copied into the scratch
-    flags, n_heavy, _, _ = classify(nnz_row)
-    SPGEMM_STATS["rows"], SPGEMM_STATS["heavy_or_declined"] = n_row, n_heavy
+    flags, n_heavy, _, _ = _spgemm_classify(p, prod, cap, nnz_row)
     if n_heavy:
-        iota = torch.empty(max(n_row, int(a_indices.numel())) + 1, dtype=torch.int64, device=dev)
-        _ffi.call("spamd_iota", int(iota.numel()), ptr(iota), s)
-        heavy_rows = compact(iota[:n_row], flags, exclusive_scan(flags), n_heavy)
-        a_rows = csr_to_keys(a_indptr, torch.zeros_like(a_indices), n_row, 1)   # row id of every A element
-        nA = int(a_indices.numel())
-        eflags = new_flags(nA, dev)
-        _ffi.call("spamd_gather", 8, nA, ptr(flags), ptr(a_rows), ptr(eflags), s)
-        eflags[nA:] = 0
-        eoff = exclusive_scan(eflags)
-        sel = compact(iota[:nA], eflags, eoff, int(eoff[-1]))               # A elements of those rows
-        hkeys, hvals = _spgemm_keys(n_row, n_col, gather(a_data, sel), gather(a_indices, sel), gather(a_rows, sel), b_data,
-                                    b_indices, b_indptr)
-        hptr, hidx = keys_to_csr(hkeys, n_row, n_col, torch.int64)
-        _ffi.call("spamd_spgemm_unpack", vcode, n_heavy, ptr(heavy_rows.contiguous()), ptr(hptr),
-                  ptr(hidx), ptr(hvals.contiguous()), ptr(prod_off), ptr(tmp_cols), ptr(tmp_vals), ptr(nnz_row), s)
+        _spgemm_merge_heavy(p, flags, n_heavy, prod_off, tmp_cols, tmp_vals, nnz_row)
     out_ptr = exclusive_scan(nnz_row)
     nnz = int(out_ptr[-1])
     out_idx = torch.empty(nnz, dtype=torch.int64, device=dev)
-    out_val = torch.empty(nnz, dtype=dtr, device=dev)
+    out_val = torch.empty(nnz, dtype=p.dtr, device=dev)
     zeros = torch.empty(1, dtype=torch.int64, device=dev)
-    _ffi.call("spamd_spgemm_pack", vcode, n_row, ptr(prod_off), ptr(out_ptr), ptr(tmp_cols), ptr(tmp_vals), ptr(out_idx),
+    _ffi.call("spamd_spgemm_pack", p.vcode, n_row, ptr(prod_off), ptr(out_ptr), ptr(tmp_cols), ptr(tmp_vals), ptr(out_idx),
               ptr(out_val), ptr(zeros), s)
     note_zero_bits_count(out_val, zeros)
-    return out_val, out_idx, out_ptr
+    return (out_val, out_idx, out_ptr), n_heavy
+
+
+def _spgemm(n_row, n_col, a_data, a_indices, a_indptr, b_data, b_indices, b_indptr, a_rows=None, row_local_only=False):
+    """A @ B along `_spgemm_route`: ((data, int64 indices, int64 indptr), None) from the first row-local step that delivers,
+    else (None, (keys, data)) from the global form - or (None, None) with `row_local_only`.  A is given by its pointers, by
+    the row id of every element (`a_rows`, of a COO: its pointers are built when a row-local step wants them) or by both.
+    The only writer of SPGEMM_STATS: `route` = small/first | small/second | bitmap | buckets | global is what delivered;
+    `kernel`, `rows`, `heavy_or_declined` (and `parts`) with a row-local delivery - `kernel` = "buckets" also when the bucket
+    path hands the whole product to the global form; `max_prod`, `max_arow`, `products` once the probe has run; the bitmap
+    kernel's `bitmap_failed` (since the probe), `bitmap_refused`, `phase_cycles`."""
+    dtr = torch_dtype(dot_dtype(a_data.dtype, b_data.dtype))
+    nnz_a = int(a_data.numel())
+    steps = _spgemm_route(n_row, n_col, nnz_a, dtr)
+    row_local = steps[0][0] != "global"
+    if not row_local and row_local_only:
+        return None, None
+    if row_local and a_indptr is None:
+        a_indptr = rows_to_indptr(a_rows, n_row)
+    p = _spgemm_operands(n_row, n_col, dtr, a_data, a_indices, a_indptr, b_data, b_indices, b_indptr, a_rows, row_local)
+    probe = None
+    while steps:
+        step, steps = steps[0], steps[1:]
+        kind, arg = step[0], step[1:]
+        if kind == "probe":
+            probe = _spgemm_probe(p)
+            SPGEMM_STATS.update(max_prod=probe[3], max_arow=probe[4], products=probe[2])
+            SPGEMM_STATS.pop("bitmap_failed", None)
+            steps = _spgemm_route(n_row, n_col, nnz_a, dtr, probe[2:])
+        elif kind == "small":
+            try:
+                res = _spgemm_small_run(p, arg[0])
+            except torch.OutOfMemoryError:       # (its buffers hold min(cells, products) entries: the other kernels need less)
+                if arg[0] is None:
+                    raise
+                res = None
+            if res is not None:
+                SPGEMM_STATS.update(kernel="small", rows=n_row, heavy_or_declined=0, route="small/first" if arg[0] is None else "small/second")
+                return res, None
+        elif kind == "bitmap":
+            res, seen = _spgemm_bitmap(p, arg[0], probe[2])
+            for key, value in seen.items():
+                SPGEMM_STATS[key] = value if key == "phase_cycles" else SPGEMM_STATS.get(key, 0) + value
+            if res is not None:
+                SPGEMM_STATS.update(rows=n_row, heavy_or_declined=0, kernel="bitmap", parts=arg[0], route="bitmap")
+                return res, None
+        elif kind == "buckets":
+            SPGEMM_STATS["kernel"] = "buckets"
+            out = _spgemm_buckets(p, *probe)
+            if out is not None:
+                SPGEMM_STATS.update(rows=n_row, heavy_or_declined=out[1], route="buckets")
+                return out[0], None
+        elif not row_local_only:
+            keys = _spgemm_keys(p)
+            SPGEMM_STATS["route"] = "global"
+            return None, keys
+    return None, None
+
+
+def _spgemm_small(n_row, n_col, a_data, a_indices, a_indptr, b_data, b_indices, b_indptr):
+    """The one-launch kernel alone, whatever the route's switches say (a test calls it): (data, int64 indices, int64 indptr),
+    or None when the operands are outside its limits or B is not canonical.  Writes no statistics."""
+    dtr = torch_dtype(dot_dtype(a_data.dtype, b_data.dtype))
+    if not _spgemm_small_fits(_spgemm_vcode(dtr), n_row, n_col):
+        return None
+    return _spgemm_small_run(_spgemm_operands(n_row, n_col, dtr, a_data, a_indices, a_indptr, b_data, b_indices, b_indptr))
+
+
+def _spgemm_rows(n_row, n_col, a_data, a_indices, a_indptr, b_data, b_indices, b_indptr):
+    """The row-local steps of `_spgemm` alone: (data, int64 indices, int64 indptr) of A @ B from the first of the small,
+    bitmap and bucket kernels that delivers; None when the route is the global form's or every step declined (the caller
+    then uses the global form throughout)."""
+    return _spgemm(n_row, n_col, a_data, a_indices, a_indptr, b_data, b_indices, b_indptr, row_local_only=True)[0]
 
 
 def dot_csr_csr(out_shape, a_data, b_data, a_indices, b_indices, a_indptr, b_indptr):
     """CSR @ CSR -> (data, indices, indptr) with int64 indices — `_dot_csr_csr`
     (reference _common.py:639-717).  Explicit zeros are kept (the GCXS constructor prunes)."""
     n_row, n_col = int(out_shape[0]), int(out_shape[1])
-    if SPGEMM_ROW_LOCAL:
-        res = _spgemm_rows(n_row, n_col, a_data, a_indices, a_indptr, b_data, b_indices, b_indptr)
-        if res is not None:
-            return res
-    a_rows = csr_to_keys(a_indptr, torch.zeros_like(a_indices), n_row, 1)  # row id of every A element
-    keys, data = _spgemm_keys(n_row, n_col, a_data, a_indices, a_rows, b_data, b_indices, b_indptr)
-    indptr, indices = keys_to_csr(keys, n_row, n_col, torch.int64)
-    return data, indices, indptr
+    res, keys = _spgemm(n_row, n_col, a_data, a_indices, a_indptr, b_data, b_indices, b_indptr)
+    if res is not None:
+        return res
+    indptr, indices = keys_to_csr(keys[0], n_row, n_col, torch.int64)
+    return keys[1], indices, indptr
 
 
 def dot_coo_coo(out_shape, a_coords, b_coords, a_data, b_data, n_inner):
@@ -1182,16 +1306,10 @@ def dot_coo_coo(out_shape, a_coords, b_coords, a_data, b_data, n_inner):
     construction of reference _common.py:450-475,907-976.  `n_inner` = a.shape[1] = b.shape[0]."""
     n_row, n_col = int(out_shape[0]), int(out_shape[1])
     b_indptr = rows_to_indptr(b_coords[0], int(n_inner))
-    if SPGEMM_ROW_LOCAL:
-        a_indptr = rows_to_indptr(a_coords[0], n_row)
-        res = _spgemm_rows(n_row, n_col, a_data, a_coords[1], a_indptr, b_data, b_coords[1], b_indptr)
-        if res is not None:
-            data, indices, indptr = res
-            keys = csr_to_keys(indptr, indices, n_row, n_col)
-            return delinearize(keys, (n_row, n_col), torch.int64), data
-    a_rows = convert(a_coords[0].contiguous(), torch.int64)
-    keys, data = _spgemm_keys(n_row, n_col, a_data, a_coords[1], a_rows, b_data, b_coords[1], b_indptr)
-    return delinearize(keys, (n_row, n_col), torch.int64), data
+    res, keys = _spgemm(n_row, n_col, a_data, a_coords[1], None, b_data, b_coords[1], b_indptr, a_rows=a_coords[0])
+    if res is not None:
+        keys = csr_to_keys(res[2], res[1], n_row, n_col), res[0]
+    return delinearize(keys[0], (n_row, n_col), torch.int64), keys[1]
 
 
 SDDMM_PANEL_BYTES = 3 << 20     # Bt rows of one column panel: what stays in a 4 MiB L2 next to the streamed operands

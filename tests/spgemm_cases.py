@@ -5,12 +5,16 @@ width or a size exactly where the code switches path.  No GPU, no torch, no pack
 
 The reference sums every output element left to right in the order of A's elements, starting from zero of the result type,
 with a separately rounded multiply and add: what the library promises bit for bit on every route but the grouped reduce.
-The numbers the table is aimed at are the constants below; tests/test_spgemm_cases.py reads every one of them from the source
-text (`source_constants`), so a retune that moves a boundary fails there instead of silently un-aiming the table.
+The numbers the table is aimed at are the constants below; tests/test_spgemm_cases.py reads the kernels' from the text of the
+.hip sources and of _reduce.py (`source_constants`) and the host's from `sparse_amd._kernels` itself (its `SPGEMM_*` values),
+so a retune that moves a boundary fails there instead of silently un-aiming the table.
 
 A case builds its operands for a value size (4 or 8 bytes: the row classes, the capacity and the small kernel's widths depend
-on it) and states the route the product must take under the switches it sets and the `heavy_or_declined` count that
-`SPGEMM_STATS` must then report (`parts` is the bitmap kernel's word: no case here takes it, and it must stay unset); `predict` derives the same from the host's rules and `bucket_model`."""
+on it) and states the route the product must take under the switches it sets - what `SPGEMM_STATS["route"]` must then say -
+and the `heavy_or_declined` count beside it (`parts` is the bitmap kernel's word: no case here takes it, and it must stay
+unset).  `predict` derives the same from a restatement of the host's rules and `bucket_model`, independent of the one choice
+the library makes (`_kernels._spgemm_route`); tests/test_spgemm_cases.py feeds that function every case's own numbers and
+holds the steps it returns against `predict`."""
 import functools
 import math
 import os
@@ -144,7 +148,7 @@ def source_constants():
         assert m, f"{what}: `{pattern}` is gone from the source - move the cases of tests/spgemm_cases.py with it"
         return m
 
-    rows, small, kern, red = src("csrc", "spgemm_rows.hip"), src("csrc", "spgemm_small.hip"), src("_kernels.py"), src("_reduce.py")
+    rows, small, red = src("csrc", "spgemm_rows.hip"), src("csrc", "spgemm_small.hip"), src("_reduce.py")
     out = {"SPG_BUCKET_MAX": int(grab(rows, r"constexpr int SPG_BUCKET_MAX = (\d+);", "SPG_BUCKET_MAX")[1])}
     m = grab(rows, r"static constexpr int MID = sizeof\(KEY\) \+ sizeof\(V\) <= (\d+) \? (\d+) : (\d+);", "MID")
     out["MID"] = tuple(int(x) for x in m.groups())
@@ -176,16 +180,6 @@ def source_constants():
     out["sm_lds_kb"], out["sm_reserve"] = int(m[1]), int(m[2])
     grab(small, r"if \(n_col <= sm_max_cols<V>\(4\)\) \{", "the four-wave switch")
     grab(small, r"\} else if \(n_col <= sm_max_cols<V>\(1\)\) \{", "the one-wave switch")
-    out["SMALL_MAX_CELLS"] = 1 << int(grab(kern, r"SPGEMM_SMALL_MAX_CELLS = 1 << (\d+)", "SPGEMM_SMALL_MAX_CELLS")[1])
-    out["SMALL_MAX_NNZ"] = 1 << int(grab(kern, r"SPGEMM_SMALL_MAX_NNZ = 1 << (\d+)", "SPGEMM_SMALL_MAX_NNZ")[1])
-    grab(kern, r"n_row \* n_col <= SPGEMM_SMALL_MAX_CELLS and int\(a_data\.numel\(\)\) <= SPGEMM_SMALL_MAX_NNZ", "the first chance")
-    grab(kern, r"four_waves = \(\(64 \* 1024\) // 4 - 32\) \* 8 // \(8 \* es \+ 1\)", "four_waves")
-    grab(kern, r"return fill >= 1\.0 or \(n_col <= four_waves and fill >= 0\.25\)", "the second chance")
-    out["RUN_PROBE_MIN"] = 1 << int(grab(kern, r"SPGEMM_RUN_PROBE_MIN = 1 << (\d+)", "SPGEMM_RUN_PROBE_MIN")[1])
-    out["RUN_DUPS_MIN"] = int(grab(kern, r"P >= SPGEMM_RUN_PROBE_MIN and P - c >= (\d+) and", "the run probe")[1])
-    grab(kern, r"if n_heavy \* 4 > n_row or heavy_products \* 4 > total \* 3 or n_arow_only:", "the fall-back rule")
-    grab(kern, r"if max_prod > cap or max_arow > cap:", "the heavy-row test")
-    grab(kern, r"if n_col >= 2 \*\* 31 - 1 or n_row == 0:", "the column limit of the host")
     out["LONG_RUN_WINDOW"] = int(grab(red, r"LONG_RUN_WINDOW = (\d+)", "LONG_RUN_WINDOW")[1])
     return out
 
@@ -452,6 +446,15 @@ DEFAULT_SWITCHES = {"SPGEMM_ROW_LOCAL": True, "SPGEMM_SMALL": True, "SPGEMM_SMAL
                     "SPGEMM_SMALL_MAX_CELLS": SMALL_MAX_CELLS, "SPGEMM_SMALL_MAX_NNZ": SMALL_MAX_NNZ}
 
 
+def mostly_heavy(st, vb):
+    """the bucket path's own decline: rows above the capacity (by their products or by their A elements) that are more than
+    a quarter of the rows or hold more than three quarters of the products, or a row heavy by its A elements alone"""
+    cap = bounds(st.key_bytes, vb)[4]
+    by_prod, by_a = st.prod > cap, st.alen > cap
+    heavy = by_prod | by_a
+    return bool(heavy.any() and (heavy.sum() * 4 > st.n_row or int(st.prod[heavy].sum()) * 4 > int(st.prod.sum()) * 3 or (by_a & ~by_prod).any()))
+
+
 def predict(st, dtype, switches):
     """(route, heavy_or_declined) of `_spgemm_rows` / `dot_csr_csr` by the rules of _kernels.py, the bitmap kernel switched off:
     route = small/first | small/second | buckets | global"""
@@ -474,10 +477,8 @@ def predict(st, dtype, switches):
     kb = st.key_bytes
     cap = bounds(kb, vb)[4]
     by_prod, by_a = st.prod > cap, st.alen > cap
-    if by_prod.any() or by_a.any():
-        heavy = by_prod | by_a
-        if heavy.sum() * 4 > st.n_row or int(st.prod[heavy].sum()) * 4 > total * 3 or (by_a & ~by_prod).any():
-            return "global", None
+    if mostly_heavy(st, vb):
+        return "global", None
     declined = [r for r in range(st.n_row) if not (by_prod[r] or by_a[r]) and not served(st.n_col, kb, vb, st.columns_of_row(r))]
     return "buckets", int((by_prod | by_a).sum()) + len(declined)
 
@@ -972,6 +973,24 @@ def slug(name):
 
 
 assert len({slug(n) for n in CASES}) == len(CASES)
+
+# the smallest case of every route with float32 values, by the stored elements of A and B (the first of the table on a tie;
+# `buckets` with no row and with a row left to the global form): what the C-ABI calls of one product are counted on
+SMALLEST = {"small/first": "small: n_col = 1", "small/second": "small: second chance, fill == 1/4 at n_col = four_waves",
+            "buckets": "an empty B", "buckets/heavy": "zeros: buckets, a heavy row merged from the global form",
+            "global": "n_col = 2^31 - 1: declined, the global form answers"}
+
+
+def smallest_cases():
+    """the same, worked out from the table"""
+    best = {}
+    for name, c in CASES.items():
+        if "float32" in c.dtypes:
+            st = case_struct(name, 4)
+            key = "buckets/heavy" if c.route == "buckets" and c.heavy else c.route
+            if key not in best or st.ai.size + st.bi.size < best[key][0]:
+                best[key] = (st.ai.size + st.bi.size, name)
+    return {key: name for key, (_, name) in best.items()}
 
 
 def runs():

@@ -661,15 +661,18 @@ def _int_valued(sp, g, dtype, seed):
     return sp.GCXS((v, g.indices, g.indptr), shape=g.shape, compressed_axes=g.compressed_axes)
 
 
-def _spgemm_audit(sp, a, b, kernel, stats_check=None):
-    """the raw triple and its zero-bit note before the container prunes, then the container"""
+def _spgemm_audit(sp, a, b, kernel, stats_check=None, route=None):
+    """the raw triple and its zero-bit note before the container prunes, then the container; `route`: what `SPGEMM_STATS`
+    names beside `kernel` (the kernel's own name, "global" without one, unless given: the small kernel's two chances)"""
     from sparse_amd import _kernels as K
 
     ops = Untouched(a, b)
     K.SPGEMM_STATS.clear()
     data, indices, indptr = K.dot_csr_csr((a.shape[0], b.shape[1]), a.data, b.data, a.indices, b.indices, a.indptr, b.indptr)
     stats = dict(K.SPGEMM_STATS)
+    route = route or kernel or "global"
     assert stats.get("kernel") == kernel, stats              # (None: no row-local kernel ran, the global form throughout)
+    assert stats["route"] == route, stats
     if stats_check is not None:
         stats_check(stats)
     hd = _npy(data)
@@ -683,7 +686,7 @@ def _spgemm_audit(sp, a, b, kernel, stats_check=None):
         assert int(note[0]) == zeros, (note, zeros)
     K.SPGEMM_STATS.clear()
     c = a @ b
-    assert K.SPGEMM_STATS.get("kernel") == kernel, dict(K.SPGEMM_STATS)
+    assert K.SPGEMM_STATS.get("kernel") == kernel and K.SPGEMM_STATS["route"] == route, dict(K.SPGEMM_STATS)
     assert isinstance(c, sp.GCXS) and c.nnz == hd.size - zeros
     audit(sp, c, pruned=True, operands=ops.ops)
     ops.check()
@@ -702,11 +705,11 @@ def test_spgemm_routes_give_canonical_products(sp, dtype, idt, monkeypatch):
 
     # the one-launch kernel
     a, b = operand((200, 300), 0.05, 1), operand((300, 250), 0.05, 2)
-    _spgemm_audit(sp, a, b, "small")
+    _spgemm_audit(sp, a, b, "small", route="small/first")
     # its second chance, once the row products are known (tests/test_round6_gpu.py, 700 x 900 with 120 per row)
     a, b = operand((700, 900), 120 / 900, 11), operand((900, 900), 120 / 900, 12)
     assert a.nnz > K.SPGEMM_SMALL_MAX_NNZ
-    _spgemm_audit(sp, a, b, "small")
+    _spgemm_audit(sp, a, b, "small", route="small/second")
     monkeypatch.setattr(K, "SPGEMM_SMALL_SECOND", False)
     _spgemm_audit(sp, a, b, "buckets")
     monkeypatch.undo()

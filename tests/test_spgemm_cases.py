@@ -1,8 +1,10 @@
-"""tests/spgemm_cases.py on its own, without a GPU: the constants the table was built for against the source text, the
-reference against the CPU oracle and against a dense exact product, its signed zeros, its sensitivity to the order of A's
-elements, and the table against every boundary it claims - product counts, classes, buckets, passes, key bits, fill, cells,
-window alignment, and the route and `heavy_or_declined` count that follow from them by the host's rules.  A boundary that a
-case claims and does not meet is a failure here, not a weaker GPU test."""
+"""tests/spgemm_cases.py on its own, without a GPU: the constants the table was built for against the kernels' source text
+and the host module's values, the reference against the CPU oracle and against a dense exact product, its signed zeros, its
+sensitivity to the order of A's elements, and the table against every boundary it claims - product counts, classes, buckets,
+passes, key bits, fill, cells, window alignment, and the route and `heavy_or_declined` count that follow from them by the
+host's rules.  A boundary that a case claims and does not meet is a failure here, not a weaker GPU test.  Then the library's
+one choice of route, `_kernels._spgemm_route` (pure: the built library answers its limit queries without a device), on
+every case's own numbers against that model, and on a table with a case on each side of every threshold."""
 import numpy as np
 import pytest
 
@@ -42,9 +44,13 @@ def test_constants_in_the_source_are_the_ones_the_table_was_built_for():
     assert src["N_COL_LIMIT"] == sc.N_COL_LIMIT == 2147483647
     assert (src["sm_lds_kb"], src["sm_reserve"]) == (64, 32)
     assert [sc.sm_max_cols(vb, w) for vb in (4, 8) for w in (4, 1)] == [3964, 15879, 2012, 8062]
-    assert (src["SMALL_MAX_CELLS"], src["SMALL_MAX_NNZ"]) == (sc.SMALL_MAX_CELLS, sc.SMALL_MAX_NNZ) == (1 << 22, 1 << 16)
-    assert (src["RUN_PROBE_MIN"], src["RUN_DUPS_MIN"], src["LONG_RUN_WINDOW"]) == (sc.RUN_PROBE_MIN, sc.RUN_DUPS_MIN, sc.LONG_RUN_WINDOW)
+    from sparse_amd import _kernels as K          # the host's constants: the module's own values
+
+    assert (K.SPGEMM_SMALL_MAX_CELLS, K.SPGEMM_SMALL_MAX_NNZ) == (sc.SMALL_MAX_CELLS, sc.SMALL_MAX_NNZ) == (1 << 22, 1 << 16)
+    assert (K.SPGEMM_RUN_PROBE_MIN, K.SPGEMM_RUN_DUPS_MIN, src["LONG_RUN_WINDOW"]) == (sc.RUN_PROBE_MIN, sc.RUN_DUPS_MIN, sc.LONG_RUN_WINDOW)
     assert sc.RUN_DUPS_MIN == sc.LONG_RUN_WINDOW - 1 == 1023 and sc.RUN_PROBE_MIN == 8192
+    for name, value in sc.DEFAULT_SWITCHES.items():
+        assert getattr(K, name) == value, name
     assert [sc.spg_bits(n) for n in (0, 1, 2, 3, 4, 2 ** 27 - 1, 2 ** 27, 2 ** 31 - 2)] == [1, 1, 2, 2, 3, 27, 28, 31]
     assert sc.key_bits(2 ** 27 - 1, 32) == 32 and sc.key_bits(2 ** 27 - 1, 33) == 33
 
@@ -228,3 +234,208 @@ def test_the_table_covers_what_it_set_out_to():
                    "zeros: buckets", "zeros: global"):
         assert any(needle in n for n in names), needle
     assert len(sc.calls()) == len(set(sc.calls())) and 400 < len(sc.calls()) < 1000
+
+
+def test_the_smallest_case_of_every_route_is_the_one_named():
+    assert sc.smallest_cases() == sc.SMALLEST
+
+
+# ---- the library's one choice of route --------------------------------------------------------------------------------------
+P, G = ("probe",), ("global",)
+F = ("small", None)           # the first chance
+B = (("buckets",), G)
+
+
+def _steps(K, n_row, n_col, nnz_a, dtype, products):
+    """every step `_kernels._spgemm` would walk if each one declined: the route before the probe, then - where it ends in the
+    probe and the probe's findings are given - the route after it"""
+    import torch
+
+    dtr = getattr(torch, dtype)
+    steps = K._spgemm_route(n_row, n_col, nnz_a, dtr)
+    if steps[-1] == P and products is not None:
+        steps += K._spgemm_route(n_row, n_col, nnz_a, dtr, products)
+    return steps
+
+
+def _route_names(steps):
+    return ["small/first" if s == F else "small/second" if s[0] == "small" else s[0] for s in steps if s != P]
+
+
+@pytest.mark.parametrize("name", list(sc.CASES), ids=sc.slug)
+def test_the_librarys_route_on_every_case_is_the_models(hiplib, monkeypatch, name):
+    """`_spgemm_route` on the case's own numbers, under the case's switches: the route `predict` states is among the steps and
+    nothing stands before it - but the bucket kernels before a global product, where the model's mostly-heavy rule holds (the
+    device's counts decide that: a decline of the executor, not a rule of the route)"""
+    from sparse_amd import _kernels as K
+
+    c = sc.CASES[name]
+    for switch, value in {**c.switches, **c.patch}.items():
+        monkeypatch.setattr(K, switch, value)
+    for dtype in c.dtypes:
+        vb = sc.value_bytes(dtype)
+        st = sc.case_struct(name, vb)
+        route, _ = sc.predict(st, dtype, c.switches)
+        products = (int(st.prod.sum()), int(st.prod.max(initial=0)), st.max_arow)
+        steps = _steps(K, st.n_row, st.n_col, st.ai.size, dtype, products)
+        names = _route_names(steps)
+        assert route in names, (dtype, route, steps)
+        before = names[:names.index(route)]
+        if route == "global":
+            assert steps == (G,) or (steps == (P, *B) and sc.mostly_heavy(st, vb)), (dtype, steps)
+        else:
+            assert before == [], (dtype, route, steps)                 # (`buckets`: the first step after the probe)
+            assert steps[0] == (F if route == "small/first" else P), (dtype, steps)   # (the first chance: before any device read)
+
+
+@pytest.mark.parametrize("dtype", sc.REAL_TYPES)
+def test_the_second_chance_takes_a_quarter_fill_up_to_four_waves_columns(hiplib, dtype):
+    """the route's own copy of `sm_max_cols(4)` is the kernel's: at that many columns a quarter product per cell goes to the
+    small kernel, just below a quarter and one column further it does not"""
+    from sparse_amd import _kernels as K
+
+    n = sc.sm_max_cols(np.dtype(dtype).itemsize, 4)
+    nnz_a = K.SPGEMM_SMALL_MAX_NNZ + 1                  # (no first chance)
+    for n_col, total, takes in ((n, n, True), (n, n - 1, False), (n + 1, n + 1, False), (n + 1, n, False)):
+        steps = _steps(K, 4, n_col, nnz_a, dtype, (total, total, 4))
+        assert steps == ((P, ("small", total), *B) if takes else (P, *B)), (n_col, total, steps)
+
+
+_M9 = {"SPGEMM_BITMAP_MAX_DUPS": 10 ** 9}
+_M9W = {"SPGEMM_BITMAP_MAX_DUPS": 10 ** 9, "SPGEMM_BITMAP_SPLIT": False}
+_W = {"SPGEMM_BITMAP_SPLIT": False}
+_MEAN0 = {"SPGEMM_BITMAP_MIN_MEAN": 0}
+
+# (id, n_row, n_col, stored elements of A, value type, what the probe finds (total, max_prod, max_arow) or None, switches, steps).
+# The steps were evaluated with the predicates of the commit before `_spgemm_route` - the branch conditions of its `_spgemm_rows`,
+# `dot_csr_csr` and `_spgemm_small`, its `_spgemm_small_second` and `_spgemm_bitmap_forms`, with the built library's limits -
+# on these numbers: a case on each side of every threshold, for 4-byte and 8-byte values.  70000 elements of A: no first
+# chance.  `bool`: that commit's `_spgemm_rows` raised `code_of`'s TypeError; the route now hands the type to the global form,
+# whose `product_code` raises it (checked below).
+_SPGEMM_ROUTES = [
+    ("float32-cells-2^22", 1024, 4096, 100, "float32", (1000, 10, 3), {}, (F, P, *B)),
+    ("float32-cells-2^22+4096", 1025, 4096, 100, "float32", (1000, 10, 3), {}, (P, *B)),
+    ("float32-nnz-2^16", 257, 64, 65536, "float32", (1000, 10, 3), {}, (F, P, *B)),
+    ("float32-nnz-2^16+1", 257, 64, 65537, "float32", (1000, 10, 3), {}, (P, *B)),
+    ("float32-ncol-max_cols", 4, 15879, 100, "float32", (1000, 10, 3), {}, (F, P, *B)),
+    ("float32-ncol-max_cols+1", 4, 15880, 100, "float32", (1000, 10, 3), {}, (P, *B)),
+    ("float32-ncol-0", 4, 0, 100, "float32", (0, 0, 2), {}, (P, *B)),
+    ("float32-ncol-1", 4, 1, 100, "float32", (3, 1, 2), {}, (F, P, ("small", 3), *B)),
+    ("float32-nrow-0", 0, 50, 0, "float32", None, {}, (G,)),
+    ("float32-nrow-1", 1, 50, 3, "float32", (9, 9, 3), {}, (F, P, *B)),
+    ("float32-ncol-2^31-2", 4, 2147483646, 15, "float32", (10, 6, 2), {}, (P, *B)),
+    ("float32-ncol-2^31-1", 4, 2147483647, 15, "float32", None, {}, (G,)),
+    ("float32-total-0-bitmap-mean-0", 5, 100000, 70000, "float32", (0, 0, 2), _MEAN0, (P, *B)),
+    ("float32-total-1-bitmap-mean-0", 5, 100000, 70000, "float32", (1, 1, 2), _MEAN0, (P, ("bitmap", 1), *B)),
+    ("float32-fill-1", 4, 6000, 70000, "float32", (24000, 6000, 60), {}, (P, ("small", 24000), *B)),
+    ("float32-fill-below-1", 4, 6000, 70000, "float32", (23999, 6000, 60), {}, (P, *B)),
+    ("float32-fill-1/4-four_waves", 4, 3964, 70000, "float32", (3964, 3964, 4), {}, (P, ("small", 3964), *B)),
+    ("float32-fill-below-1/4-four_waves", 4, 3964, 70000, "float32", (3963, 3963, 4), {}, (P, *B)),
+    ("float32-fill-1/4-four_waves+1", 4, 3965, 70000, "float32", (3965, 3965, 4), {}, (P, *B)),
+    ("float32-fill-1-four_waves+1", 4, 3965, 70000, "float32", (15860, 3965, 4), {}, (P, ("small", 15860), *B)),
+    ("float32-buffer-2^30", 1048576, 2000, 4194304, "float32", (1073741824, 2000, 4), {}, (P, ("small", 1073741824), *B)),
+    ("float32-buffer-2^30+1", 1048576, 2000, 4194304, "float32", (1073741825, 2000, 4), {}, (P, *B)),
+    ("float32-second-ncol-max_cols", 4, 15879, 70000, "float32", (63516, 15879, 4), {}, (P, ("small", 63516), *B)),
+    ("float32-second-ncol-max_cols+1", 4, 15880, 70000, "float32", (63520, 15880, 4), {}, (P, *B)),
+    ("float32-mean-1300", 100, 1000000, 70000, "float32", (130000, 2000, 50), {}, (P, ("bitmap", 1), *B)),
+    ("float32-mean-below-1300", 100, 1000000, 70000, "float32", (129999, 2000, 50), {}, (P, *B)),
+    ("float32-arow-limit", 100, 1000000, 70000, "float32", (200000, 2000, 256), {}, (P, ("bitmap", 1), *B)),
+    ("float32-arow-limit+1", 100, 1000000, 70000, "float32", (200000, 2000, 257), {}, (P, *B)),
+    ("float32-maxprod-limit", 100, 1000000, 70000, "float32", (2000000, 16384, 50), _M9W, (P, ("bitmap", 1), *B)),
+    ("float32-maxprod-limit+1", 100, 1000000, 70000, "float32", (2000000, 16385, 50), _M9W, (P, *B)),
+    ("float32-maxprod-limit+1-split", 100, 1000000, 70000, "float32", (2000000, 16385, 50), _M9, (P, ("bitmap", 3), *B)),
+    ("float32-ncol-limit", 100, 1048576, 70000, "float32", (200000, 2000, 50), _W, (P, ("bitmap", 1), *B)),
+    ("float32-ncol-limit+1", 100, 1048577, 70000, "float32", (200000, 2000, 50), _W, (P, *B)),
+    ("float32-ncol-limit+1-split", 100, 1048577, 70000, "float32", (200000, 2000, 50), {}, (P, ("bitmap", 3), *B)),
+    ("float32-dups-7745", 100, 250000, 70000, "float32", (400000, 7745, 50), _W, (P, ("bitmap", 1), *B)),
+    ("float32-dups-7746", 100, 250000, 70000, "float32", (400000, 7746, 50), _W, (P, *B)),
+    ("float32-split-parts-64", 100, 1000000, 70000, "float32", (100000000, 497618, 50), _M9, (P, ("bitmap", 64), *B)),
+    ("float32-split-parts-65", 100, 1000000, 70000, "float32", (100000000, 497619, 50), _M9, (P, *B)),
+    ("float32-split-dups-18973", 100, 1000000, 70000, "float32", (10000000, 18973, 50), {}, (P, ("bitmap", 3), *B)),
+    ("float32-split-dups-18974", 100, 1000000, 70000, "float32", (10000000, 18974, 50), {}, (P, *B)),
+    ("float32-both-forms-split-True", 100, 1000000, 70000, "float32", (200000, 2000, 50), {"SPGEMM_BITMAP_SPLIT": True}, (P, ("bitmap", 1), *B)),
+    ("float32-split-only-split-True", 100, 3000000, 70000, "float32", (200000, 2000, 50), {"SPGEMM_BITMAP_SPLIT": True}, (P, ("bitmap", 7), *B)),
+    ("float32-both-forms-split-False", 100, 1000000, 70000, "float32", (200000, 2000, 50), _W, (P, ("bitmap", 1), *B)),
+    ("float32-split-only-split-False", 100, 3000000, 70000, "float32", (200000, 2000, 50), _W, (P, *B)),
+    ("float32-both-forms-split-first", 100, 1000000, 70000, "float32", (200000, 2000, 50), {"SPGEMM_BITMAP_SPLIT": "first"}, (P, ("bitmap", 3), ("bitmap", 1), *B)),
+    ("float32-split-only-split-first", 100, 3000000, 70000, "float32", (200000, 2000, 50), {"SPGEMM_BITMAP_SPLIT": "first"}, (P, ("bitmap", 7), *B)),
+    ("float32-row-local-off", 7, 30, 40, "float32", (100, 20, 3), {"SPGEMM_ROW_LOCAL": False}, (G,)),
+    ("float32-small-off", 7, 30, 40, "float32", (210, 30, 6), {"SPGEMM_SMALL": False}, (P, *B)),
+    ("float32-small-on", 7, 30, 40, "float32", (210, 30, 6), {}, (F, P, ("small", 210), *B)),
+    ("float32-second-off", 4, 6000, 70000, "float32", (24000, 6000, 60), {"SPGEMM_SMALL_SECOND": False}, (P, *B)),
+    ("float32-bitmap-off", 100, 1000000, 70000, "float32", (200000, 2000, 50), {"SPGEMM_BITMAP": False}, (P, *B)),
+    ("float64-cells-2^22", 1024, 4096, 100, "float64", (1000, 10, 3), {}, (F, P, *B)),
+    ("float64-cells-2^22+4096", 1025, 4096, 100, "float64", (1000, 10, 3), {}, (P, *B)),
+    ("float64-nnz-2^16", 257, 64, 65536, "float64", (1000, 10, 3), {}, (F, P, *B)),
+    ("float64-nnz-2^16+1", 257, 64, 65537, "float64", (1000, 10, 3), {}, (P, *B)),
+    ("float64-ncol-max_cols", 4, 8062, 100, "float64", (1000, 10, 3), {}, (F, P, *B)),
+    ("float64-ncol-max_cols+1", 4, 8063, 100, "float64", (1000, 10, 3), {}, (P, *B)),
+    ("float64-ncol-0", 4, 0, 100, "float64", (0, 0, 2), {}, (P, *B)),
+    ("float64-ncol-1", 4, 1, 100, "float64", (3, 1, 2), {}, (F, P, ("small", 3), *B)),
+    ("float64-nrow-0", 0, 50, 0, "float64", None, {}, (G,)),
+    ("float64-nrow-1", 1, 50, 3, "float64", (9, 9, 3), {}, (F, P, *B)),
+    ("float64-ncol-2^31-2", 4, 2147483646, 15, "float64", (10, 6, 2), {}, (P, *B)),
+    ("float64-ncol-2^31-1", 4, 2147483647, 15, "float64", None, {}, (G,)),
+    ("float64-total-0-bitmap-mean-0", 5, 100000, 70000, "float64", (0, 0, 2), _MEAN0, (P, *B)),
+    ("float64-total-1-bitmap-mean-0", 5, 100000, 70000, "float64", (1, 1, 2), _MEAN0, (P, ("bitmap", 1), *B)),
+    ("float64-fill-1", 4, 6000, 70000, "float64", (24000, 6000, 60), {}, (P, ("small", 24000), *B)),
+    ("float64-fill-below-1", 4, 6000, 70000, "float64", (23999, 6000, 60), {}, (P, *B)),
+    ("float64-fill-1/4-four_waves", 4, 2012, 70000, "float64", (2012, 2012, 4), {}, (P, ("small", 2012), *B)),
+    ("float64-fill-below-1/4-four_waves", 4, 2012, 70000, "float64", (2011, 2011, 4), {}, (P, *B)),
+    ("float64-fill-1/4-four_waves+1", 4, 2013, 70000, "float64", (2013, 2013, 4), {}, (P, *B)),
+    ("float64-fill-1-four_waves+1", 4, 2013, 70000, "float64", (8052, 2013, 4), {}, (P, ("small", 8052), *B)),
+    ("float64-buffer-2^30", 1048576, 2000, 4194304, "float64", (1073741824, 2000, 4), {}, (P, ("small", 1073741824), *B)),
+    ("float64-buffer-2^30+1", 1048576, 2000, 4194304, "float64", (1073741825, 2000, 4), {}, (P, *B)),
+    ("float64-second-ncol-max_cols", 4, 8062, 70000, "float64", (32248, 8062, 4), {}, (P, ("small", 32248), *B)),
+    ("float64-second-ncol-max_cols+1", 4, 8063, 70000, "float64", (32252, 8063, 4), {}, (P, *B)),
+    ("float64-mean-1300", 100, 1000000, 70000, "float64", (130000, 2000, 50), {}, (P, ("bitmap", 1), *B)),
+    ("float64-mean-below-1300", 100, 1000000, 70000, "float64", (129999, 2000, 50), {}, (P, *B)),
+    ("float64-arow-limit", 100, 1000000, 70000, "float64", (200000, 2000, 256), {}, (P, ("bitmap", 1), *B)),
+    ("float64-arow-limit+1", 100, 1000000, 70000, "float64", (200000, 2000, 257), {}, (P, *B)),
+    ("float64-maxprod-limit", 100, 1000000, 70000, "float64", (2000000, 8192, 50), _M9W, (P, ("bitmap", 1), *B)),
+    ("float64-maxprod-limit+1", 100, 1000000, 70000, "float64", (2000000, 8193, 50), _M9W, (P, *B)),
+    ("float64-maxprod-limit+1-split", 100, 1000000, 70000, "float64", (2000000, 8193, 50), _M9, (P, ("bitmap", 3), *B)),
+    ("float64-ncol-limit", 100, 1020672, 70000, "float64", (200000, 2000, 50), _W, (P, ("bitmap", 1), *B)),
+    ("float64-ncol-limit+1", 100, 1020673, 70000, "float64", (200000, 2000, 50), _W, (P, *B)),
+    ("float64-ncol-limit+1-split", 100, 1020673, 70000, "float64", (200000, 2000, 50), {}, (P, ("bitmap", 3), *B)),
+    ("float64-dups-7745", 100, 250000, 70000, "float64", (400000, 7745, 50), _W, (P, ("bitmap", 1), *B)),
+    ("float64-dups-7746", 100, 250000, 70000, "float64", (400000, 7746, 50), _W, (P, *B)),
+    ("float64-split-parts-64", 100, 1000000, 70000, "float64", (100000000, 242296, 50), _M9, (P, ("bitmap", 64), *B)),
+    ("float64-split-parts-65", 100, 1000000, 70000, "float64", (100000000, 242297, 50), _M9, (P, *B)),
+    ("float64-split-dups-9486", 100, 250000, 70000, "float64", (10000000, 9486, 50), {}, (P, ("bitmap", 3), *B)),
+    ("float64-split-dups-9487", 100, 250000, 70000, "float64", (10000000, 9487, 50), {}, (P, *B)),
+    ("float64-both-forms-split-True", 100, 1000000, 70000, "float64", (200000, 2000, 50), {"SPGEMM_BITMAP_SPLIT": True}, (P, ("bitmap", 1), *B)),
+    ("float64-split-only-split-True", 100, 3000000, 70000, "float64", (200000, 2000, 50), {"SPGEMM_BITMAP_SPLIT": True}, (P, ("bitmap", 7), *B)),
+    ("float64-both-forms-split-False", 100, 1000000, 70000, "float64", (200000, 2000, 50), _W, (P, ("bitmap", 1), *B)),
+    ("float64-split-only-split-False", 100, 3000000, 70000, "float64", (200000, 2000, 50), _W, (P, *B)),
+    ("float64-both-forms-split-first", 100, 1000000, 70000, "float64", (200000, 2000, 50), {"SPGEMM_BITMAP_SPLIT": "first"}, (P, ("bitmap", 3), ("bitmap", 1), *B)),
+    ("float64-split-only-split-first", 100, 3000000, 70000, "float64", (200000, 2000, 50), {"SPGEMM_BITMAP_SPLIT": "first"}, (P, ("bitmap", 7), *B)),
+    ("float64-row-local-off", 7, 30, 40, "float64", (100, 20, 3), {"SPGEMM_ROW_LOCAL": False}, (G,)),
+    ("float64-small-off", 7, 30, 40, "float64", (210, 30, 6), {"SPGEMM_SMALL": False}, (P, *B)),
+    ("float64-small-on", 7, 30, 40, "float64", (210, 30, 6), {}, (F, P, ("small", 210), *B)),
+    ("float64-second-off", 4, 6000, 70000, "float64", (24000, 6000, 60), {"SPGEMM_SMALL_SECOND": False}, (P, *B)),
+    ("float64-bitmap-off", 100, 1000000, 70000, "float64", (200000, 2000, 50), {"SPGEMM_BITMAP": False}, (P, *B)),
+    ("complex64", 7, 30, 40, "complex64", (100, 20, 3), {}, (G,)),
+    ("complex128", 7, 30, 40, "complex128", (100, 20, 3), {}, (G,)),
+    ("bool", 7, 30, 40, "bool", (100, 20, 3), {}, (G,)),
+    ("int32", 7, 30, 40, "int32", (100, 20, 3), {}, (F, P, ("small", 100), *B)),
+    ("int64", 7, 30, 40, "int64", (100, 20, 3), {}, (F, P, ("small", 100), *B)),
+]
+
+
+@pytest.mark.parametrize("case", _SPGEMM_ROUTES, ids=[c[0] for c in _SPGEMM_ROUTES])
+def test_spgemm_route_table(hiplib, monkeypatch, case):
+    """`_kernels._spgemm_route`, the one choice of kernel for `sparse @ sparse`: the first chance of the small kernel, whether
+    the row-product probe is worth a launch, then the second chance, the forms of the bitmap kernel, the bucket kernels and
+    the global form"""
+    import torch
+
+    from sparse_amd import _kernels as K
+
+    _, n_row, n_col, nnz_a, dtype, products, switches, want = case
+    for switch, value in switches.items():
+        monkeypatch.setattr(K, switch, value)
+    assert _steps(K, n_row, n_col, nnz_a, dtype, products) == want
+    if dtype == "bool":
+        with pytest.raises(TypeError):
+            K.product_code(getattr(torch, dtype))

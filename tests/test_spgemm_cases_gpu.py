@@ -62,8 +62,8 @@ def _force(monkeypatch, K, case):
 
 
 def _observed_route(stats):
-    """`_spgemm_rows` writes `rows` when one of its kernels delivered the product, and `max_prod` once the first chance of the
-    small kernel is behind it; the global form writes nothing"""
+    """the route from the other keys, as before `route` was one: `rows` is written when a row-local kernel delivered the
+    product, and `max_prod` once the first chance of the small kernel is behind it; the global form writes neither"""
     if "rows" not in stats:
         return "global"
     if stats["kernel"] == "small":
@@ -113,7 +113,7 @@ def _dot_csr_csr(K, grouped, call):
     torch.cuda.synchronize()
     stats = dict(K.SPGEMM_STATS)
     route = "global" if np.dtype(dtype).kind == "c" else case.route
-    assert _observed_route(stats) == route, stats
+    assert _observed_route(stats) == route and stats["route"] == route, stats
     if route != "global":
         assert stats["heavy_or_declined"] == case.heavy and stats["rows"] == st.n_row, stats
     assert stats.get("parts") is None, stats                      # (the bitmap kernel's word: no case of this table takes it)
@@ -145,7 +145,8 @@ def _matmul_of_containers(K, call, container):
     K.SPGEMM_STATS.clear()
     c = a @ b
     torch.cuda.synchronize()
-    assert _observed_route(dict(K.SPGEMM_STATS)) == ("global" if np.dtype(dtype).kind == "c" else case.route), dict(K.SPGEMM_STATS)
+    route = "global" if np.dtype(dtype).kind == "c" else case.route
+    assert _observed_route(dict(K.SPGEMM_STATS)) == route and K.SPGEMM_STATS["route"] == route, dict(K.SPGEMM_STATS)
     assert isinstance(c, sp.GCXS if container == "gcxs" else sp.COO) and c.shape == (st.n_row, st.n_col)
     bits = sc.bits_of(data)
     keep = bits.any(axis=1) if bits.ndim == 2 else bits != 0           # the bit-wise prune: -0.0 would stay
@@ -172,6 +173,40 @@ def test_case(K, monkeypatch, grouped, run):
         _dot_csr_csr(K, grouped, call)
         for container in ("gcxs", "coo"):
             _matmul_of_containers(K, call, container)
+
+
+# C-ABI calls of one `dot_csr_csr` (differences of `_ffi.CALLS`), measured on the commit before `_spgemm_route`: the smallest
+# case of every route with float32 values, and the smallest shape of tests/test_spgemm_bitmap_gpu.py with the bitmap kernel
+# forced on as that file forces it
+CALLS_BEFORE = {"small/first": 2, "small/second": 5, "buckets": 7, "buckets/heavy": 27, "global": 10, "bitmap": 4}
+
+
+def test_no_route_makes_more_c_abi_calls_than_it_did(K, monkeypatch):
+    from sparse_amd import _ffi
+    from test_spgemm_bitmap_gpu import _csr
+
+    def calls(shape, A, B):
+        (ad, ai, ap), (bd, bi, bp) = (tuple(dev(x) for x in A), tuple(dev(x) for x in B))
+        K.SPGEMM_STATS.clear()
+        c0 = _ffi.CALLS
+        K.dot_csr_csr(shape, ad, bd, ai, bi, ap, bp)
+        return _ffi.CALLS - c0, dict(K.SPGEMM_STATS)
+
+    assert set(sc.SMALLEST) | {"bitmap"} == set(CALLS_BEFORE)
+    for key, name in sc.SMALLEST.items():
+        case = sc.CASES[name]
+        with monkeypatch.context() as m:
+            _force(m, K, case)
+            st = sc.case_struct(name, 4)
+            got, stats = calls((st.n_row, st.n_col), *sc.case_operands(name, "float32", (case.pools or sc.pools_of("float32"))[0]))
+        assert stats["route"] == case.route and (stats.get("heavy_or_declined", 0) > 0) == (key == "buckets/heavy"), (key, stats)
+        assert got <= CALLS_BEFORE[key], (key, got)
+    with monkeypatch.context() as m:
+        for name, value in (("SPGEMM_BITMAP", True), ("SPGEMM_BITMAP_MIN_MEAN", 0), ("SPGEMM_BITMAP_MAX_DUPS", 10 ** 9), ("SPGEMM_BITMAP_SPLIT", False)):
+            m.setattr(K, name, value)
+        got, stats = calls((1, 1_048_576), _csr(1, 3_000, 120, 11), _csr(3_000, 1_048_576, 110, 11))
+    assert stats["route"] == "bitmap" and stats["parts"] == 1, stats
+    assert got <= CALLS_BEFORE["bitmap"], got
 
 
 def test_switches_are_back_where_they_were(K):
